@@ -2,13 +2,19 @@
 """bench.py -- whole hot path (k-mer count + differential filter + window map + enrichment)
 on a synthetic genome resident in HBM.  One "step" = one full pass over the genome.
 
-    python bench.py --gpus 1 --steps K --warmup W [--config wheat|peanut|ara|small|tiny]
+    python bench.py --gpus 1 --steps K --warmup W [--config wheat|peanut|ara|small|tiny] [--full] [--dump-outputs DIR]
 
 Prints ONE JSON line (rank 0).  metric = genome Gbases/s (BASELINE.json); dtype names
 the arithmetic type of the dominant work (u32 counters); `roofline` prices the dominant
-kernel against 8 TB/s HBM using the ALGORITHMIC bytes of SURVEY.md section 8(d);
-`cpu_baseline` is the oracle (a C port, oracle/sp_oracle.c) timed on this box's host
-cores over a bounded sample of the same workload.
+kernel against 8 TB/s HBM using the ALGORITHMIC bytes of SURVEY.md section 8(d), from the
+HIP events of the timed steps.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full` adds what
+takes runs of its own: `cpu_baseline` (the oracle, a C port in oracle/sp_oracle.c, timed on
+the host cores over a bounded sample of the same workload, then the same sample redone on
+the GPU and compared: `verified`) and `ms_per_step_no_events` (the steps once more without
+the per-launch events).  `--dump-outputs DIR` writes what the last timed step returned as
+DIR/<name>.npy (float32 / float64, at most 64 MB; see write_outputs).
 """
 import argparse
 import json
@@ -43,7 +49,15 @@ def parse():
                          "one rank (the line then carries dist_selfcheck.ok); this flag turns it on for --force-dist runs")
     ap.add_argument("--no-dist-selfcheck", action="store_true", help="skip the self-check of a multi-rank run")
     ap.add_argument("--cpu-sample-mb", type=float, default=float(os.environ.get("SP_CPU_SAMPLE_MB", "1000")))
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check what takes runs of its own: the CPU baseline with its in-run verification "
+                         "against the oracle (unless --no-cpu-baseline) and the steps once more without per-launch events")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 # host wall-clock phases of DistHotPath that contain a collective (reported per rank as `exchange_ms_per_rank`)
@@ -209,22 +223,27 @@ def main():
     dt = time.perf_counter() - t0
     ctx.prof_enable(False)
     prof = ctx.prof_report()
-    # the same steps once more WITHOUT the two HIP events per launch that the roofline figures are made of (they cost
-    # ~1 % of a wheat-like pass and ~10 % of an Arabidopsis-like one): reported next to the contract's figure, never as it
-    n_plain = min(args.steps, 3)
     wall_timed = dict((hp if runner is None else runner).wall)      # (the stage walls of the timed steps only)
-    barrier()
-    t1 = time.perf_counter()
-    for _ in range(n_plain):
-        a, b = step()
-    barrier()
-    dt_plain = time.perf_counter() - t1
+    if args.dump_outputs and rank == 0:
+        # now, before anything else runs: the rows and tables live in context-owned page-locked buffers the next pass reuses
+        write_outputs(args.dump_outputs, a, b)
+    dt_plain = 0.0
+    if args.full:
+        # the same steps once more WITHOUT the two HIP events per launch that the roofline figures are made of (they cost
+        # ~1 % of a wheat-like pass and ~10 % of an Arabidopsis-like one): reported next to the contract's figure, never as it
+        n_plain = min(args.steps, 3)
+        barrier()
+        t1 = time.perf_counter()
+        for _ in range(n_plain):
+            a, b = step()
+        barrier()
+        dt_plain = time.perf_counter() - t1
     if dist is not None:
         t = torch.tensor([dt, dt_plain], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt, dt_plain = float(t[0].item()), float(t[1].item())
     ms_per_step = dt / args.steps * 1e3
-    ms_per_step_no_events = dt_plain / n_plain * 1e3
+    ms_per_step_no_events = round(dt_plain / n_plain * 1e3, 3) if args.full else None
     gbases = gen.total_bases / (dt / args.steps) / 1e9
     # what every rank spent waiting for / issuing the table (or key-range) exchange and the other collectives
     rank_wall = rank_local = None
@@ -380,13 +399,13 @@ def main():
 
     # ---- CPU baseline: the oracle on this box's host cores, bounded sample ---------------------
     cpu = None
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         cpu = cpu_baseline(ctx, gen, d_ascii, kmer_labels, args)
 
     out = {
         "metric": "genome Gbases/s k-mer+enrichment, %s k=%d 1Mb windows" % (args.config, args.k),
         "value": round(gbases, 4), "unit": "Gbases/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_step_no_events": round(ms_per_step_no_events, 3),
+        "warmup": args.warmup, "ms_per_step": round(ms_per_step, 3), "ms_per_step_no_events": ms_per_step_no_events,
         "higher_is_better": True,
         "scaling": "strong", "vs_baseline": None, "dtype": "u32", "data": "synthetic",
         "config": {"workload": "%s-like synthetic genome, %d chromosomes, %.3f Gbases, k=%d, lower_count=3, "
@@ -421,6 +440,74 @@ def main():
         time.sleep(1.0)       # let the other ranks' buffered library output drain first
     print(json.dumps(out))
     sys.stdout.flush()
+
+
+DUMP_LIMIT = 64_000_000      # bytes, every file --dump-outputs writes together
+DUMP_SEED = 8017
+
+
+def _dump_rows(n, row_bytes, budget, salt):
+    """rows to keep of an n-row output: all of them when they fit `budget` bytes, else a fixed, seeded sample (ascending;
+    the same rows whenever n is the same)"""
+    cap = max(1, int(budget // row_bytes))
+    if n <= cap:
+        return np.arange(n)
+    return np.sort(np.random.default_rng([DUMP_SEED, salt]).choice(n, cap, replace=False))
+
+
+def write_outputs(path, a, b):
+    """--dump-outputs: what one pass (count_and_filter -> a, map_and_enrich -> b) returned to its caller, as float32 /
+    float64 DIR/<name>.npy, so that two builds can be compared output for output:
+      tallies                    n_union, n_rows, n_hist, n_mapped
+      kmer_lengths               per chromosome
+      matrix_*                   the differential rows in ascending key order: the key as two 32-bit halves (exact at any
+                                 k), the per-chromosome counts, the row totals; matrix_rows = each row's rank in key order
+      bin_counts, bin_offsets    the per-bin subgenome counts of every chromosome, concatenated, and where each chromosome
+                                 starts; bin_rows = which bins
+      window_*                   the non-empty windows: chromosome, window index, counts, p-values, ratios, argmin, sig
+    A group larger than its share of the 64 MB is a fixed, seeded sample of its rows (the *_rows files say which)."""
+    f64 = lambda x: np.asarray(x, np.float64)                                    # noqa: E731
+    out = {"tallies": f64([a.n_union, a.n_rows, a.n_hist, b.n_mapped]), "kmer_lengths": f64(a.kmer_lengths)}
+
+    keys = np.asarray(a.keys, np.uint64)[:int(a.n_rows)]
+    counts = np.asarray(a.counts)[:len(keys)]
+    tot = None if a.tot is None else np.asarray(a.tot)[:len(keys)]
+    rows = _dump_rows(len(keys), 8 * (counts.shape[1] + 4), 36e6, 1)
+    o = np.argsort(keys, kind="stable")[rows]
+    out["matrix_rows"] = f64(rows)
+    out["matrix_key_hi"] = f64(keys[o] >> np.uint64(32))
+    out["matrix_key_lo"] = f64(keys[o] & np.uint64(0xFFFFFFFF))
+    out["matrix_counts"] = f64(counts[o])
+    if tot is not None:
+        out["matrix_tot"] = f64(tot[o])
+
+    bins = [np.asarray(x) for x in b.bins]
+    if bins:
+        allb = np.concatenate(bins)
+        dt = np.float32 if allb.size == 0 or int(allb.max()) < (1 << 24) else np.float64    # exact either way
+        rows = _dump_rows(len(allb), np.dtype(dt).itemsize * allb.shape[1] + 8, 20e6, 2)
+        out["bin_rows"] = f64(rows)
+        out["bin_offsets"] = f64(np.cumsum([0] + [len(x) for x in bins]))
+        out["bin_counts"] = allb[rows].astype(dt)
+
+    win = np.asarray(b.window_counts)
+    rows = _dump_rows(len(win), 8 * (3 * win.shape[1] + 5), 6e6, 3)
+    out["window_rows"] = f64(rows)
+    out["window_chrom"] = f64(np.asarray(b.coord_chrom)[rows])
+    out["window_index"] = f64(np.asarray(b.coord_win)[rows])
+    out["window_counts"] = f64(win[rows])
+    out["window_pvals"] = f64(np.asarray(b.pvals)[rows])
+    out["window_ratios"] = f64(np.asarray(b.ratios)[rows])
+    out["window_argmin"] = f64(np.asarray(b.argmin)[rows])
+    out["window_sig"] = f64(np.asarray(b.sig)[rows])
+
+    total = sum(v.nbytes + 128 for v in out.values())          # (+ the .npy header)
+    if total > DUMP_LIMIT:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT))
+    os.makedirs(path, exist_ok=True)
+    for name, v in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(v))
+    return sorted(out)
 
 
 def cpu_baseline(ctx, gen, d_ascii, kmer_labels, args):

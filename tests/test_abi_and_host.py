@@ -432,6 +432,68 @@ def test_bench_selfchecks_multi_rank_runs_by_default(monkeypatch):
     assert "exchange wait" in bench.EXCHANGE_KEYS and "exchange+lengths" in bench.EXCHANGE_KEYS
 
 
+def test_bench_plain_run_options(monkeypatch):
+    """A plain run does only what its headline needs: --full and --dump-outputs are off unless given, --steps is the
+    number of timed steps (at least one)."""
+    import importlib.util
+    import sys
+    spec = importlib.util.spec_from_file_location("bench_mod3", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    def parse(argv):
+        monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+        return bench.parse()
+    a = parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = parse(["--steps", "1", "--warmup", "0", "--full", "--dump-outputs", "out"])
+    assert a.full is True and a.dump_outputs == "out"
+    with pytest.raises(SystemExit):
+        parse(["--steps", "0"])
+
+
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs writes one pass's results as float32 / float64 .npy, within 64 MB, rows in key order, keys exact
+    at k = 32, a seeded sample (the same on every call) where a group is too large, and nothing else."""
+    import importlib.util
+    from types import SimpleNamespace
+    spec = importlib.util.spec_from_file_location("bench_mod4", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    rng = np.random.default_rng(5)
+    M, C, S, W = 400_000, 21, 3, 5000                       # 400 K x 21 rows: more than the matrix share of 64 MB
+    keys = rng.choice(np.iinfo(np.int64).max, M, replace=False).astype(np.uint64) * np.uint64(2) + np.uint64(1)
+    counts = rng.integers(0, 1 << 31, (M, C)).astype(np.uint32)
+    a = SimpleNamespace(n_union=10 * M, n_rows=M, n_hist=77, kmer_lengths=np.arange(C) + 10**9, keys=keys, counts=counts,
+                        tot=counts.sum(axis=1, dtype=np.uint64))
+    bins = [rng.integers(0, 10000, (n, S)).astype(np.int32) for n in (700_000, 1_300_000)]
+    b = SimpleNamespace(n_mapped=12345, bins=bins, window_counts=rng.integers(0, 10**6, (W, S)),
+                        coord_chrom=np.repeat([0, 1], W // 2), coord_win=np.arange(W), pvals=rng.random((W, S)),
+                        ratios=rng.random((W, S)), argmin=rng.integers(0, S, W).astype(np.int32), sig=rng.random(W) < 0.5)
+    names = bench.write_outputs(str(tmp_path / "x"), a, b)
+    assert bench.write_outputs(str(tmp_path / "y"), a, b) == names
+    files = sorted(os.listdir(tmp_path / "x"))
+    assert files == sorted(n + ".npy" for n in names)
+    assert sum(os.path.getsize(tmp_path / "x" / f) for f in files) <= 64_000_000
+    got = {}
+    for f in files:
+        x, y = np.load(tmp_path / "x" / f), np.load(tmp_path / "y" / f)
+        assert x.dtype in (np.float32, np.float64), f
+        assert np.array_equal(x, y), f
+        got[f[:-4]] = x
+    assert list(got["tallies"]) == [10 * M, M, 77, 12345]
+    rows = got["matrix_rows"].astype(np.int64)
+    assert 0 < len(rows) < M and (np.diff(rows) > 0).all()
+    k = got["matrix_key_hi"].astype(np.uint64) << np.uint64(32) | got["matrix_key_lo"].astype(np.uint64)
+    o = np.argsort(keys)[rows]
+    assert (k == keys[o]).all() and (np.diff(k.astype(np.float64)) >= 0).all()
+    assert (got["matrix_counts"] == counts[o]).all() and (got["matrix_tot"] == a.tot[o]).all()
+    allb = np.concatenate(bins)
+    assert list(got["bin_offsets"]) == [0, 700_000, 2_000_000]
+    assert (got["bin_counts"] == allb[got["bin_rows"].astype(np.int64)]).all()
+    assert len(got["window_rows"]) == W and (got["window_pvals"] == b.pvals).all() and (got["window_sig"] == b.sig).all()
+
+
 def test_bench_jellyfish_leg(tmp_path, monkeypatch):
     """bench.py's cpu_baseline leg runs the reference's exact jellyfish commands (Jellyfish.py:697-699) when the
     binary exists and diffs its dump with the oracle's; this image has none -> "absent".  With a stand-in executable

@@ -151,7 +151,8 @@ def test_bench_line_single_and_forced_dist(tmp_path):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT="29533", HSA_ENABLE_IPC_MODE_LEGACY="0")
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "2", "--warmup", "1",
-                          "--cpu-sample-mb", "5"], capture_output=True, text=True, env=env, timeout=600)
+                          "--cpu-sample-mb", "5", "--full", "--dump-outputs", str(tmp_path / "full")],
+                         capture_output=True, text=True, env=env, timeout=600)
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads(out.stdout.strip().splitlines()[-1])
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "dtype",
@@ -160,6 +161,26 @@ def test_bench_line_single_and_forced_dist(tmp_path):
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["verified"] is True and d["unit"] == "Gbases/s"
     assert d["roofline"]["bound"] == "hbm" and 0 < d["roofline"]["frac"] < 1 and d["roofline"]["traffic"] is None
     assert d["cpu_baseline"]["kind"] == "port" and d["cpu_baseline"]["jellyfish"] in ("absent",) or isinstance(d["cpu_baseline"]["jellyfish"], dict)
+    assert d["ms_per_step_no_events"] > 0
+    # the plain run: the same headline fields, none of what --full adds, and the same outputs of its last step
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path / "plain")], capture_output=True, text=True, env=env, timeout=600)
+    assert out.returncode == 0, out.stderr[-2000:]
+    dp = json.loads(out.stdout.strip().splitlines()[-1])
+    for key in ("metric", "unit", "higher_is_better", "dtype"):
+        assert dp[key] == d[key], key
+    assert dp["value"] > 0 and dp["steps"] == 3 and dp["ms_per_step"] > 0 and dp["cpu_baseline"] is None and dp["ms_per_step_no_events"] is None
+    assert dp["config"] == d["config"]
+    import numpy as np
+    names = sorted(p.name for p in (tmp_path / "full").iterdir())
+    assert names == sorted(p.name for p in (tmp_path / "plain").iterdir()) and "matrix_counts.npy" in names
+    assert sum((tmp_path / "plain" / n).stat().st_size for n in names) <= 64_000_000
+    for n in names:
+        x, y = np.load(tmp_path / "full" / n), np.load(tmp_path / "plain" / n)
+        assert x.dtype in (np.float32, np.float64) and x.dtype == y.dtype and x.shape == y.shape, n
+        assert np.array_equal(x, y, equal_nan=True), n
+    t = np.load(tmp_path / "plain" / "tallies.npy")
+    assert t[1] == d["config"]["differential_kmers"] and t[0] == d["config"]["union_kmers"] and t[3] == d["config"]["mapped_positions"]
     out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--config", "small", "--steps", "2", "--warmup", "1",
                           "--no-cpu-baseline", "--force-dist", "--dist-selfcheck"], capture_output=True, text=True, env=env,
                          timeout=600)

@@ -2,11 +2,11 @@
 # PMC passes of one round on the GPU box (run through gpurun from the repo root).  Each group is its own
 # rocprofv3 run (--pmc with --kernel-trace only: MI355X_MICROARCH.md; gpurun refuses other combinations).
 #   usage: tools/pmc_round.sh <tag> [bench args...]
-# Output: gpurun_out/<tag>_pmc.json (per kernel, per launch averages) + gpurun_out/<tag>_kernel_stats.md
+# Output (under $SP_OUT, default out/): <tag>_pmc.json (per kernel, per launch averages) + <tag>_kernel_stats.md
 set -u
 TAG=${1:-r02}; shift || true
 R=${GRAFT_REPO_ROOT:-$PWD}
-O=$R/gpurun_out
+O=${SP_OUT:-$R/out}
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
 GROUPS_=("FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum TCC_REQ_sum TCC_READ_sum"
