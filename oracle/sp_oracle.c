@@ -551,7 +551,7 @@ double spo_hypergeom_right_tail(int64_t a, int64_t b, int64_t c, int64_t d) {
         long double x = (long double)a;
         long double term = expl(lchoosel(K, x) + lchoosel(N - K, n - x) - logden);
         long double s = term;
-        while (x < (long double)hi) {
+        while (x < (long double)hi && term > 0.0L) {
             term *= (K - x) * (n - x) / ((x + 1.0L) * (N - K - n + x + 1.0L));
             x += 1.0L;
             s += term;
@@ -562,7 +562,7 @@ double spo_hypergeom_right_tail(int64_t a, int64_t b, int64_t c, int64_t d) {
         long double x = (long double)a - 1.0L;
         long double term = expl(lchoosel(K, x) + lchoosel(N - K, n - x) - logden);
         long double s = term;
-        while (x > (long double)lo) {
+        while (x > (long double)lo && term > 0.0L) {   /* an underflowed term: the rest is smaller still */
             term *= x * (N - K - n + x) / ((K - x + 1.0L) * (n - x + 1.0L));
             x -= 1.0L;
             s += term;

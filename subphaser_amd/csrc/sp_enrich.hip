@@ -220,12 +220,14 @@ __device__ double d_betacf(double a, double b, double x) {
     }
     return h;
 }
-__device__ double d_betainc(double a, double b, double x) {
+// I_x(a, b) with y = 1 - x formed by the caller without cancellation: for a small t, x = df / (df + t^2) rounds
+// next to 1 and 1 - x would keep only a few digits of t^2 / (df + t^2) (p near 1 was 5e-12 off at df = 126)
+__device__ double d_betainc(double a, double b, double x, double y) {
     if (!(x > 0.0)) return 0.0;
     if (!(x < 1.0)) return 1.0;
-    const double bt = exp(lgamma(a + b) - lgamma(a) - lgamma(b) + a * log(x) + b * log1p(-x));
+    const double bt = exp(lgamma(a + b) - lgamma(a) - lgamma(b) + a * log(x) + b * log(y));
     if (x < (a + 1.0) / (a + b + 2.0)) return bt * d_betacf(a, b, x) / a;
-    return 1.0 - bt * d_betacf(b, a, 1.0 - x) / b;
+    return 1.0 - bt * d_betacf(b, a, y) / b;
 }
 
 __global__ void __launch_bounds__(128)
@@ -272,7 +274,7 @@ k7_ttest(const uint32_t *__restrict__ counts, long long M, int C, const double *
         const double t = (mu[0] - mu[1]) / denom;
         if (t != t) p = t;                               // 0 / 0: NaN, kept by the caller like the reference does
         else if (isinf(t)) p = 0.0;
-        else p = d_betainc(0.5 * df, 0.5, df / (df + t * t));
+        else p = d_betainc(0.5 * df, 0.5, df / (df + t * t), t * t / (df + t * t));
     }
     pvals[r] = p;
 }

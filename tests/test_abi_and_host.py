@@ -624,7 +624,7 @@ def test_cli_entry_point_leaves_without_teardown(tmp_path):
     import subprocess
     import sys
     out = subprocess.run([sys.executable, "-m", "subphaser_amd", "-h"], cwd=ROOT, capture_output=True, text=True, timeout=120)
-    assert out.returncode == 0 and "-sg_cfgs" in out.stdout or "sg_cfgs" in out.stdout
+    assert out.returncode == 0 and ("-sg_cfgs" in out.stdout or "sg_cfgs" in out.stdout)
     marker, atexit_marker = tmp_path / "written", tmp_path / "atexit"
     prog = ("import atexit, sys\n"
             "from subphaser_amd import pipeline\n"

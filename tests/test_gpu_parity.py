@@ -119,7 +119,7 @@ def test_count_engine2_hot_slots(gpu_ctx, k):
 
 def test_count_engine2_big_buckets_on_16_bit_counters(gpu_ctx):
     """Round 6: c2_count16 counts the fine buckets of 65536 records and more as well (their adds check for a wrapped half; a bucket
-    with a wrapped counter is handed to c2_count) and writes the pairs of saturated slots (>= 255) straight to the bucket's segment
+    with a wrapped counter is recounted in place on 32-bit half tables, no c2_count launch) and writes the pairs of saturated slots (>= 255) straight to the bucket's segment
     of the staging list.  k = 9 on 34 Mb of random sequence: four fine buckets of ~8 M records, about half of their 32768 slots at
     255 or more; then the same with a 100 K-copy homopolymer (a wrapped counter) in one of them."""
     rng = np.random.RandomState(909)
@@ -1116,20 +1116,35 @@ def test_fisher_cells_and_tails(gpu_ctx, golden):
 
 
 def test_enrich_vs_oracle_random(gpu_ctx):
+    """p-values against the oracle; argmin / sig against the mpmath reference on every row a kernel within the
+    reference tolerances could not turn (hp_reference.enrich_rows' fragile mask).  The 3e6 table sits at clamp scale
+    but all its p-values are 0 or 1; the wheat-like table (column totals 4e8-8e8) has informative cells."""
+    import hp_reference as hr
     rng = np.random.RandomState(44)
+    tables = []
     for S, W, scale in ((2, 300, 30), (3, 500, 200), (5, 200, 5), (3, 64, 3e6), (9, 50, 50)):
         t = rng.poisson(scale, size=(W, S)).astype(np.int64)
         t[: W // 5, 0] += rng.poisson(scale * 2 + 5, W // 5)
         t[W // 5: W // 4] = 0
+        # the 3e6 rows hold several tails that round to 1.0 (or underflow to 0): which of them is the minimum is rounding
+        # noise for any implementation, so most of those rows are fragile
+        tables.append((t, 0.2 if scale == 3e6 else 0.99))
+    tables.append((hr.wheat_table(seed=7, W=300), 0.99))
+    for t, min_nf in tables:
+        S = t.shape[1]
         with np.errstate(all="ignore"):
             gp, ga, gs, gr = gpu_ctx.enrich(t, 0.05, 0.5)
             op, oa, os_, orr = po.enrich(t, 0.05, 0.5)
         assert np.allclose(gp, op, rtol=1e-7, atol=1e-300), (S, np.abs(gp - op).max())
         assert np.abs(gp - op).max() <= 1e-6
-        same = np.isclose(gp, op, rtol=1e-12, atol=0).all(axis=1)   # decisions can only differ on p ties
-        assert (ga[same] == oa[same]).all()
-        assert (gs[same] == os_[same]).all()
+        ref = hr.enrich_rows(t, 0.05, 0.5)
+        nf = ~ref.fragile
+        assert nf.mean() >= min_nf, (S, ref.fragile.sum())
+        assert (ga[nf] == ref.argmin[nf]).all()
+        assert (gs[nf] == ref.sig[nf]).all()
         assert ((gr == orr) | (np.isnan(gr) & np.isnan(orr))).all()
+    inform = (ref.p > 1e-300) & (ref.p < 1 - 1e-12)
+    assert inform.mean() >= 0.4
 
 
 def test_enrich_needs_two_columns(gpu_ctx):
