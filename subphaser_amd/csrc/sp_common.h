@@ -34,6 +34,7 @@ struct sp_chrom {
                                       // the packing of the chromosomes after it
 };
 #define SP_PAD_WORDS 8
+#define SP_LIST_MAXC 1024    // chromosomes the list filter takes (k > 15, count engine 3): sps_join_wide above 64
 #ifndef SP_DERIVE_PM
 #define SP_DERIVE_PM 1      // the MSB-first packed stream is derived in registers instead of stored (sp_device.h)
 #endif

@@ -426,7 +426,7 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     {
         const char *env3 = getenv("SP_LIST_ENGINE");      // "0": never, "1": whenever possible (tests)
         bool whole = first == 0 && last == (int)ctx->chroms.size();
-        bool possible = whole && sp_engine2_supported(nslots) && ctx->chroms.size() <= 64;
+        bool possible = whole && sp_engine2_supported(nslots) && ctx->chroms.size() <= SP_LIST_MAXC;
         int64_t longest = 0;
         for (auto &c : ctx->chroms) {
             possible = possible && !c.tab_external;
@@ -435,9 +435,9 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
         if (engine == 3) {
             if (!possible)
                 return sp_fail(ctx, SP_EUNSUP, "count engine 3 (lists) needs k with 2^17..2^31 dense slots, a whole-genome call, "
-                                               "library-owned tables and at most 64 chromosomes");
+                                               "library-owned tables and at most %d chromosomes", SP_LIST_MAXC);
             list_mode = true;
-        } else if (engine == 0 && possible) {
+        } else if (engine == 0 && possible && ctx->chroms.size() <= 64) {     // (the automatic choice: sps_join_blk's lists)
             list_mode = (env3 && env3[0] == '1') || (!(env3 && env3[0] == '0') && longest > 0 && longest * 3 < nslots);
         }
     }

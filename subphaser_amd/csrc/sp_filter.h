@@ -111,3 +111,74 @@ __device__ __forceinline__ void sp_filter_decide(CNT &&cnt, unsigned long long t
     }
 }
 
+// One non-singleton set of sp_filter_decide on its own: 1 if the set passes the fold test (:630-641), else 0.  The
+// same operations in the same order as the loop body above (fp32 screen, fp64 quotients inside the band, the generic
+// order statistic otherwise), so the sum of this over the sets a key touches plus the all-zero result of the sets it
+// does not touch is the `include` of sp_filter_decide, bit for bit.  sps_join_wide decides set by set this way; the
+// loop above is left as it is (k3_eval and sps_join_blk are issue-bound on its code).
+template <typename CNT>
+__device__ __forceinline__ int sp_filter_set_pass(CNT &&cnt, const sp_fsets &F, int s) {
+    const int u0 = F.set_off[s], nu = F.set_off[s + 1] - u0;
+    const int bi = F.baseline < 0 ? nu + F.baseline : F.baseline;
+    double hi, lo;
+    if (bi == 1 || bi == nu - 1) {
+        {
+            float m1 = -1.0f, m2 = -1.0f, mn = 3e38f;
+            for (int u = 0; u < nu; u++) {
+                unsigned long long num = 0;
+                for (int j = F.unit_off[u0 + u]; j < F.unit_off[u0 + u + 1]; j++) num += cnt(F.unit_chrom[j]);
+                const float x = (float)num * (float)F.unit_inv[u0 + u];
+                if (x > m1) {
+                    m2 = m1;
+                    m1 = x;
+                } else if (x > m2) {
+                    m2 = x;
+                }
+                mn = x < mn ? x : mn;
+            }
+            const float thr = (float)F.min_fold * (((bi == 1) ? m2 : mn) + 1e-20f);
+            if (m1 > thr * (1.0f + 1e-5f)) return 1;
+            if (m1 < thr * (1.0f - 1e-5f)) return 0;
+        }
+        double m1 = -1.0, m2 = -1.0, mn = 1e300;
+        for (int u = 0; u < nu; u++) {
+            unsigned long long num = 0;
+            for (int j = F.unit_off[u0 + u]; j < F.unit_off[u0 + u + 1]; j++) num += cnt(F.unit_chrom[j]);
+            const double x = (double)num / F.unit_den[u0 + u];
+            if (x > m1) {
+                m2 = m1;
+                m1 = x;
+            } else if (x > m2) {
+                m2 = x;
+            }
+            mn = x < mn ? x : mn;
+        }
+        hi = m1;
+        lo = (bi == 1) ? m2 : mn;
+    } else {
+        double f[F_MAXU];
+#pragma unroll
+        for (int u = 0; u < F_MAXU; u++) {
+            f[u] = 0.0;
+            if (u < nu) {
+                unsigned long long num = 0;
+                for (int j = F.unit_off[u0 + u]; j < F.unit_off[u0 + u + 1]; j++) num += cnt(F.unit_chrom[j]);
+                f[u] = (double)num / F.unit_den[u0 + u];
+            }
+        }
+        hi = f[0];
+        lo = f[0];
+#pragma unroll
+        for (int u = 0; u < F_MAXU; u++) {
+            if (u < nu) {
+                hi = f[u] > hi ? f[u] : hi;
+                int rank = 0;
+#pragma unroll
+                for (int v = 0; v < F_MAXU; v++)
+                    if (v < nu && (f[v] > f[u] || (f[v] == f[u] && v < u))) rank++;
+                if (rank == bi) lo = f[u];
+            }
+        }
+    }
+    return (1.0 * hi / (lo + 1e-20) >= F.min_fold) ? 1 : 0;
+}

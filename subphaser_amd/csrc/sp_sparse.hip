@@ -1506,6 +1506,389 @@ sps_join_blk(sps_join_args A) {
     if (lane == 0 && uni) atomicAdd(A.n_union, uni);
 }
 
+// ------------------------------------------------------------------ sps_join_wide: the join for 64 < C <= SP_LIST_MAXC
+// sps_join_blk's layout stops at 64 lists: lane c of wave 0 owns list c, Ch[] keeps the chromosome in six bits, the share of
+// a round is BJ_T / C entries per list and every decided key gets a C-word row in LDS (at C = 1024, 64 such rows alone are
+// 256 KiB).  This kernel keeps its outputs and its staging protocol -- per-range tallies, fold-passing totals at the range's
+// closed-form place, rows in JOIN_CHUNK chunks with their rank inside the range -- so sps_tally_* / sps_place_* and the
+// row-cap retry of sps_filter_join serve both, and changes what depends on C:
+//  * the cursor logic runs on the whole workgroup: thread t owns lists t, t + WJ_THREADS, ...; the range's place, the
+//    round's pivot and the segment offsets are block reductions and scans.  A list's share of a round is proportional to
+//    what it has left, one entry at least: the shares add up to WJ_T at most (WJ_T >= 2 * SP_LIST_MAXC), the pivot is the
+//    smallest key just past a share, and the list it came from takes its whole share, so a round never overflows the hash
+//    and always moves on;
+//  * no rows in LDS.  sp_filter_decide only reads integer sums per unit, so the decision is taken set by set: the entry of
+//    a key that holds the lowest chromosome of a non-singleton set among the key's entries decides that set
+//    (sp_filter_set_pass; the other chromosomes' counts by binary search in their segments of the round, which are
+//    sorted) and adds the result less the set's all-zero result to its owner's tally.  include = (sum of the all-zero
+//    results) + tally, an integer in any order, and the ratio test is sp_filter_decide's.  SP_JOIN_GENERIC=1: the owner
+//    runs sp_filter_decide itself on the same look-ups;
+//  * kept rows are written by their entries straight into the row staging (rank * C + chromosome) after the workgroup
+//    zero-fills them.
+// LDS: 71.8 KB with 32-bit residuals (two workgroups per CU), 96.3 KB with 64-bit ones (one).
+#define WJ_THREADS 256
+#define WJ_T 2048             // entries per round
+#define WJ_H (2 * WJ_T)       // hash slots
+#define WJ_Q (WJ_T / WJ_THREADS)
+#define WJ_LPT (SP_LIST_MAXC / WJ_THREADS)    // lists per thread
+#define WJ_ROW 1u
+#define WJ_HIST 2u
+#define WJ_PEND 4u
+static_assert(WJ_T >= 2 * SP_LIST_MAXC, "a list with entries left gets a share of one entry at least");
+static_assert(SP_LIST_MAXC <= 65536 && WJ_T <= 65536, "Ch[] / Sl[] / PQ[] are 16 bits wide");
+
+struct sps_wide_args {
+    const int32_t *cset_off, *cset;   // per chromosome: the non-singleton sets it belongs to (CSR)
+    int generic;                      // SP_JOIN_GENERIC=1: sp_filter_decide per owner
+};
+
+template <typename RT>
+struct wj_lds {
+    alignas(8) RT Hk[WJ_H];           // hash keys; after the inserts: Et[WJ_T], per owner entry the sum of the key's counts
+    uint32_t Hmin[WJ_H];              // per slot: the owner entry (the lowest entry is the lowest chromosome); after the owner
+                                      // pass: Es[WJ_T] set mask -> rank among the kept rows, Ei[WJ_T] the owner's set tally
+    RT Kk[WJ_T];                      // residual keys, list by list (each segment ascending)
+    uint32_t Vv[WJ_T];
+    uint16_t Sl[WJ_T], Ch[WJ_T], PQ[WJ_T];   // Sl: hash slot, then the owner's entry; Ch: chromosome; PQ: kept rows
+    uint8_t Fl[WJ_T];                 // owners: WJ_PEND, then WJ_ROW | WJ_HIST
+    uint32_t seg_off[SP_LIST_MAXC + 1], cur[SP_LIST_MAXC];
+    unsigned long long red[WJ_THREADS / 64];
+    uint32_t scan[WJ_THREADS / 64];
+    uint32_t n_hist, n_row;
+    unsigned long long chunk_pos;
+};
+static_assert(sizeof(unsigned long long) * WJ_T <= sizeof(uint32_t) * WJ_H, "Et fits where the 32-bit hash keys were");
+
+__device__ __forceinline__ unsigned long long wj_bsum(unsigned long long v, unsigned long long *red) {
+    v = jw_sum(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long t = 0;
+#pragma unroll
+    for (int i = 0; i < WJ_THREADS / 64; i++) t += red[i];
+    __syncthreads();
+    return t;
+}
+__device__ __forceinline__ unsigned long long wj_bmin(unsigned long long v, unsigned long long *red) {
+    v = jw_min(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    unsigned long long t = ~0ULL;
+#pragma unroll
+    for (int i = 0; i < WJ_THREADS / 64; i++) t = red[i] < t ? red[i] : t;
+    __syncthreads();
+    return t;
+}
+
+template <typename RT>
+__global__ void __launch_bounds__(WJ_THREADS)
+sps_join_wide(sps_join_args A, sps_wide_args W) {
+    __shared__ wj_lds<RT> L;
+    unsigned long long *const Et = reinterpret_cast<unsigned long long *>(L.Hk);
+    uint32_t *const Es = L.Hmin;
+    int32_t *const Ei = reinterpret_cast<int32_t *>(L.Hmin + WJ_T);
+    const int C = A.C, lane = threadIdx.x & 63;
+    const sp_fsets F = A.F;
+    const RT EMPTY = (RT)~(RT)0;
+    const unsigned long long rmask = A.shift >= 64 ? ~0ULL : ((1ULL << A.shift) - 1ULL);
+    // include of a key that touches no set, and whether the set screen holds (it assumes an untouched set fails)
+    int zero_inc = 0;
+    for (int s = threadIdx.x; s < F.n_sets; s += WJ_THREADS)
+        if (F.set_off[s + 1] - F.set_off[s] > 1) zero_inc += sp_filter_set_pass([](int) -> uint32_t { return 0u; }, F, s);
+    zero_inc = (int)wj_bsum((unsigned long long)zero_inc, L.red);
+    const bool screen = A.screen && zero_inc == 0;
+    // the count of residual `res` in chromosome c's segment of the round (0: absent)
+    auto lookup = [&](int c, RT res) -> uint32_t {
+        const uint32_t e1 = L.seg_off[c + 1];
+        uint32_t lo = L.seg_off[c], hi = e1;
+        while (lo < hi) {
+            const uint32_t mid = (lo + hi) >> 1;
+            if (L.Kk[mid] < res) lo = mid + 1;
+            else hi = mid;
+        }
+        return (lo < e1 && L.Kk[lo] == res) ? L.Vv[lo] : 0u;
+    };
+    unsigned long long uni = 0;
+    unsigned long long chunk_pos = 0, chunk_end = 0;   // block-uniform
+    for (long long r = blockIdx.x; r < A.R; r += gridDim.x) {
+        uint32_t cur[WJ_LPT], endp[WJ_LPT];
+        unsigned long long start = 0;
+#pragma unroll
+        for (int j = 0; j < WJ_LPT; j++) {
+            const int c = threadIdx.x + WJ_THREADS * j;
+            cur[j] = endp[j] = 0;
+            if (c < C) {
+                cur[j] = A.bnd[(size_t)c * (size_t)(A.R + 1) + (size_t)r];
+                endp[j] = A.bnd[(size_t)c * (size_t)(A.R + 1) + (size_t)r + 1];
+            }
+            start += cur[j];
+        }
+        const unsigned long long hist_pos = wj_bsum(start, L.red);   // the range's place in the virtual concatenation
+        const unsigned long long hi_bits = A.shift >= 64 ? 0ULL : ((unsigned long long)r << A.shift);
+        uint32_t rows_before = 0, hist_before = 0;     // block-uniform
+        for (;;) {
+            // ---- the round's share of every list: everything, or everything below the pivot key
+            uint32_t take[WJ_LPT];
+            unsigned long long left_sum = 0;
+#pragma unroll
+            for (int j = 0; j < WJ_LPT; j++) {
+                take[j] = endp[j] - cur[j];
+                left_sum += take[j];
+            }
+            const unsigned long long S = wj_bsum(left_sum, L.red);
+            const bool more = S > WJ_T;                  // the shares add up to WJ_T at most
+            if (more) {
+                uint32_t q[WJ_LPT];
+                unsigned long long cand = SPS_SENTINEL;
+#pragma unroll
+                for (int j = 0; j < WJ_LPT; j++) {
+                    const uint32_t left = take[j];
+                    const uint32_t share = (uint32_t)((unsigned long long)left * (unsigned long long)(WJ_T - C) / S);
+                    q[j] = left ? (share > 1u ? share : 1u) : 0u;
+                    if (left > q[j]) {
+                        const unsigned long long x = A.lists[threadIdx.x + WJ_THREADS * j].keys[(size_t)cur[j] + q[j]];
+                        cand = x < cand ? x : cand;
+                    }
+                }
+                const unsigned long long pivot = wj_bmin(cand, L.red);     // < SENTINEL: some list has more than its share
+#pragma unroll
+                for (int j = 0; j < WJ_LPT; j++) {
+                    if (!take[j]) continue;
+                    const unsigned long long *kk = A.lists[threadIdx.x + WJ_THREADS * j].keys + cur[j];
+                    uint32_t lo = 0, hi = take[j] < q[j] ? take[j] : q[j];   // entries below the pivot lie in the share
+                    while (lo < hi) {
+                        const uint32_t mid = (lo + hi) >> 1;
+                        if (kk[mid] < pivot) lo = mid + 1;
+                        else hi = mid;
+                    }
+                    take[j] = lo;
+                }
+            }
+            uint32_t T = 0;
+#pragma unroll
+            for (int j = 0; j < WJ_LPT; j++) {
+                if (j * WJ_THREADS >= C) break;          // (block-uniform)
+                uint32_t tot;
+                const uint32_t ex = sp_block_excl_scan<uint32_t>(take[j], L.scan, tot);
+                const int c = threadIdx.x + WJ_THREADS * j;
+                if (c < C) {
+                    L.seg_off[c] = T + ex;
+                    L.cur[c] = cur[j];
+                }
+                T += tot;
+            }
+            if (threadIdx.x == 0) {
+                L.seg_off[C] = T;
+                L.n_hist = 0;
+                L.n_row = 0;
+            }
+            for (uint32_t i = threadIdx.x; i < WJ_H; i += WJ_THREADS) {
+                L.Hk[i] = EMPTY;
+                L.Hmin[i] = 0xFFFFFFFFu;
+            }
+            __syncthreads();
+            uint32_t Hn = 64;
+            while (Hn < 2 * T) Hn <<= 1;
+            // ---- load + hash-insert (owner of a key = its entry of the lowest chromosome = its lowest entry)
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                if (e < T) {
+                    int lo = 0, hi = C;       // list of entry e: last c with seg_off[c] <= e
+                    while (hi - lo > 1) {
+                        const int mid = (lo + hi) >> 1;
+                        if (L.seg_off[mid] <= e) lo = mid;
+                        else hi = mid;
+                    }
+                    const int c = lo;
+                    const size_t i = (size_t)L.cur[c] + (e - L.seg_off[c]);
+                    const sps_list li = A.lists[c];
+                    const RT res = (RT)(li.keys[i] & rmask);
+                    L.Kk[e] = res;
+                    L.Vv[e] = li.cnts[i];
+                    L.Ch[e] = (uint16_t)c;
+                    uint32_t h = (uint32_t)sps_mix((uint64_t)res) & (Hn - 1);
+                    for (;;) {
+                        const RT prev = atomicCAS(&L.Hk[h], EMPTY, res);
+                        if (prev == EMPTY || prev == res) break;
+                        h = (h + 1) & (Hn - 1);
+                    }
+                    L.Sl[e] = (uint16_t)h;
+                    atomicMin(&L.Hmin[h], e);
+                }
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                if (e < T) L.Sl[e] = (uint16_t)L.Hmin[L.Sl[e]];
+            }
+            __syncthreads();
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {       // (the totals where the hash keys were, the tallies where the slot owners were)
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                Et[e] = 0;
+                Es[e] = 0;
+                Ei[e] = 0;
+                L.Fl[e] = 0;
+            }
+            __syncthreads();
+            // ---- every entry adds itself to its owner's tallies
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                if (e < T) {
+                    const uint32_t o = L.Sl[e];
+                    if (screen) atomicOr(&Es[o], (uint32_t)A.chrom_sets[L.Ch[e]]);
+                    atomicAdd(&Et[o], (unsigned long long)L.Vv[e]);
+                }
+            }
+            __syncthreads();
+            // ---- owners: the union tally, the screen; SP_JOIN_GENERIC: the whole decision here
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                if (e < T && L.Sl[e] == e) {
+                    uni++;
+                    if (!screen || !((double)__popc(Es[e]) / (double)F.n_multi < F.ratio)) {
+                        if (W.generic) {
+                            const RT res = L.Kk[e];
+                            bool r_ = false, h_ = false;
+                            sp_filter_decide([&](int c) -> uint32_t { return lookup(c, res); }, Et[e], F, r_, h_);
+                            L.Fl[e] = (uint8_t)((r_ ? WJ_ROW : 0u) | (h_ ? WJ_HIST : 0u));
+                        } else {
+                            L.Fl[e] = (uint8_t)WJ_PEND;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+            if (!W.generic) {
+                // ---- every entry of a pending key decides the sets in which it holds the key's lowest chromosome
+#pragma unroll
+                for (int q = 0; q < WJ_Q; q++) {
+                    const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                    if (e < T) {
+                        const uint32_t o = L.Sl[e];
+                        if (L.Fl[o] & WJ_PEND) {
+                            const int c = L.Ch[e];
+                            const RT res = L.Kk[e];
+                            int d = 0;
+                            for (int m = W.cset_off[c]; m < W.cset_off[c + 1]; m++) {
+                                const int s = W.cset[m];
+                                bool first = true;
+                                for (int j = F.unit_off[F.set_off[s]]; first && j < F.unit_off[F.set_off[s + 1]]; j++) {
+                                    const int c2 = F.unit_chrom[j];
+                                    if (c2 < c && lookup(c2, res)) first = false;     // (list counts are >= 1)
+                                }
+                                if (first)
+                                    d += sp_filter_set_pass([&](int c2) -> uint32_t { return lookup(c2, res); }, F, s) -
+                                         sp_filter_set_pass([](int) -> uint32_t { return 0u; }, F, s);
+                            }
+                            if (d) atomicAdd(&Ei[o], d);
+                        }
+                    }
+                }
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < WJ_Q; q++) {
+                    const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                    if (e < T && (L.Fl[e] & WJ_PEND)) {
+                        const int include = zero_inc + Ei[e];
+                        uint32_t fl = 0;
+                        const double rr = 1.0 * (double)include / (double)F.n_multi;    // :642, as sp_filter_decide
+                        if (!(rr < F.ratio)) {
+                            fl = WJ_HIST;
+                            const double t = (double)Et[e];
+                            if (!(t < F.min_freq || t > F.max_freq)) fl |= WJ_ROW;          // :645-646
+                        }
+                        L.Fl[e] = (uint8_t)fl;
+                    }
+                }
+                __syncthreads();
+            }
+            // ---- fold-passing totals out; kept rows listed
+            bool is_row[WJ_Q];
+#pragma unroll
+            for (int q = 0; q < WJ_Q; q++) {
+                const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                const uint32_t fl = e < T ? (uint32_t)L.Fl[e] : 0u;      // (set for owners only)
+                is_row[q] = (fl & WJ_ROW) != 0;
+                const bool is_hist = (fl & WJ_HIST) != 0;
+                const unsigned long long bh = __ballot(is_hist);
+                if (bh) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&L.n_hist, (uint32_t)__popcll(bh));
+                    base = __shfl(base, 0, 64);
+                    if (is_hist)
+                        A.hist_stage[hist_pos + hist_before + base + __popcll(bh & ((1ULL << lane) - 1ULL))] = Et[e];
+                }
+                const unsigned long long br = __ballot(is_row[q]);
+                if (br) {
+                    uint32_t base = 0;
+                    if (lane == 0) base = atomicAdd(&L.n_row, (uint32_t)__popcll(br));
+                    base = __shfl(base, 0, 64);
+                    if (is_row[q]) L.PQ[base + __popcll(br & ((1ULL << lane) - 1ULL))] = (uint16_t)e;
+                }
+            }
+            __syncthreads();
+            const uint32_t nrow = L.n_row, nh = L.n_hist;
+            if (nrow) {       // rows to the staging area, ranked by key inside the round
+                if (chunk_pos + nrow > chunk_end) {      // block-uniform
+                    const unsigned long long grab = nrow > JOIN_CHUNK ? nrow : JOIN_CHUNK;
+                    if (threadIdx.x == 0) L.chunk_pos = atomicAdd(A.row_cursor, grab);
+                    __syncthreads();
+                    chunk_pos = L.chunk_pos;
+                    chunk_end = chunk_pos + grab;
+                }
+#pragma unroll
+                for (int q = 0; q < WJ_Q; q++) {
+                    if (!is_row[q]) continue;
+                    const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                    const RT res = L.Kk[e];
+                    uint32_t rank = 0;
+                    for (uint32_t j = 0; j < nrow; j++) rank += L.Kk[L.PQ[j]] < res;
+                    Es[e] = rank;
+                    const unsigned long long pos = chunk_pos + rank;
+                    if (pos < A.row_cap) {
+                        A.row_keys[pos] = hi_bits | (unsigned long long)res;
+                        A.row_tot[pos] = Et[e];
+                        A.row_rank[pos] = rows_before + rank;
+                    }
+                }
+                for (unsigned long long i = threadIdx.x; i < (unsigned long long)nrow * (unsigned long long)C; i += WJ_THREADS)
+                    if (chunk_pos + i / (unsigned long long)C < A.row_cap) A.row_counts[chunk_pos * (size_t)C + i] = 0u;
+                __threadfence();      // the zeros are out before any entry writes its count over one of them
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < WJ_Q; q++) {
+                    const uint32_t e = threadIdx.x + WJ_THREADS * q;
+                    if (e < T) {
+                        const uint32_t o = L.Sl[e];
+                        if (L.Fl[o] & WJ_ROW) {
+                            const unsigned long long pos = chunk_pos + Es[o];
+                            if (pos < A.row_cap) A.row_counts[pos * (size_t)C + L.Ch[e]] = L.Vv[e];
+                        }
+                    }
+                }
+                chunk_pos += nrow;
+                rows_before += nrow;
+            }
+            hist_before += nh;
+            __syncthreads();      // the round's LDS state is rewritten by the next round / range
+            if (!more) break;
+#pragma unroll
+            for (int j = 0; j < WJ_LPT; j++) cur[j] += take[j];
+        }
+        if (threadIdx.x == 0) {
+            A.n_rows[r] = rows_before;
+            A.n_hist[r] = hist_before;
+        }
+    }
+    uni = wj_bsum(uni, L.red);
+    if (threadIdx.x == 0 && uni) atomicAdd(A.n_union, uni);
+}
+
 // per-range tallies -> offsets: block sums, one-block scan of the sums, offsets inside every block
 #define TALLY_CHUNK 4096
 __global__ void __launch_bounds__(256)
@@ -1676,8 +2059,9 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
                            const int32_t *unit_chrom, const std::vector<double> &den, double min_fold, int baseline,
                            double min_freq, double max_freq, double ratio) {
     const int C = sps_C(ctx);
-    if (C > SPS_MAXC)
-        return sp_fail(ctx, SP_EUNSUP, "list filter (k > 15, or engine 3): at most %d chromosomes supported (got %d)", SPS_MAXC, C);
+    if (C > SP_LIST_MAXC)
+        return sp_fail(ctx, SP_EUNSUP, "list filter (k > 15, or engine 3): at most %d chromosomes supported (got %d)", SP_LIST_MAXC, C);
+    const bool wide = C > SPS_MAXC;      // sps_join_wide; up to 64 lists sps_join_blk
     int64_t total = 0, longest = 0;
     std::vector<sps_list> hl((size_t)C);
     for (int c = 0; c < C; c++) {
@@ -1699,8 +2083,9 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
         while ((1LL << bits) < ctx->nslots) bits++;
     }
     if (bits > 64) bits = 64;
-    // one workgroup per range of ~2/3 of a round
-    const int64_t per_range = (int64_t)BJ_T * 2 / 3;
+    // one workgroup per range of ~2/3 of a round; sps_join_wide: 32 entries per list (the range-edge table is C x (R + 1)
+    // words, an eighth of the lists' bytes), a range spans several rounds
+    const int64_t per_range = wide ? (int64_t)32 * C : (int64_t)BJ_T * 2 / 3;
     int rb = 0;
     while (rb < bits && rb < 23 && ((int64_t)1 << rb) * per_range < total) rb++;
     if (bits - rb > 63) rb = bits - 63;      // k = 32 and a handful of k-mers: `key >> 64` is not a shift (fuzz case k32_join)
@@ -1716,7 +2101,25 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
                  o_small = o_den + al((size_t)n_units * 16), o_cs = o_small + 256, o_bs = o_cs + al((size_t)C * 8),
                  o_rd = o_bs + 2 * al((size_t)(R / TALLY_CHUNK + 2) * 8), o_rinv = o_rd + al((size_t)BJ_FC * 4),
                  a_bytes = o_rinv + al((size_t)BJ_FC * 4);
-    int rc = sp_buf_ensure(ctx, ctx->b_sp_a, (int64_t)a_bytes);
+    // sps_join_wide: per chromosome the non-singleton sets it belongs to (CSR)
+    std::vector<int32_t> h_cso, h_cs;
+    if (wide) {
+        std::vector<std::vector<int32_t>> of((size_t)C);
+        for (int st = 0; st < n_sets; st++) {
+            if (set_off[st + 1] - set_off[st] <= 1) continue;
+            for (int j = unit_off[set_off[st]]; j < unit_off[set_off[st + 1]]; j++) {
+                std::vector<int32_t> &v = of[(size_t)unit_chrom[j]];
+                if (v.empty() || v.back() != st) v.push_back(st);
+            }
+        }
+        for (int c = 0; c < C; c++) {
+            h_cso.push_back((int32_t)h_cs.size());
+            h_cs.insert(h_cs.end(), of[(size_t)c].begin(), of[(size_t)c].end());
+        }
+        h_cso.push_back((int32_t)h_cs.size());
+    }
+    const size_t o_cso = a_bytes, o_csl = o_cso + al(h_cso.size() * 4), a_total = wide ? o_csl + al((h_cs.size() + 1) * 4) : a_bytes;
+    int rc = sp_buf_ensure(ctx, ctx->b_sp_a, (int64_t)a_total);
     if (rc) return rc;
     rc = sp_buf_ensure(ctx, ctx->b_sp_b, total * 8 + 64);
     if (rc) return rc;
@@ -1730,6 +2133,10 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
     SP_HIP(ctx, hipMemcpyAsync(A0 + o_uo, unit_off, (size_t)(n_units + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     if (n_uc) SP_HIP(ctx, hipMemcpyAsync(A0 + o_uc, unit_chrom, (size_t)n_uc * 4, hipMemcpyHostToDevice, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(A0 + o_den, den.data(), (size_t)n_units * 16, hipMemcpyHostToDevice, ctx->stream));
+    if (wide) {     // (h_cso / h_cs live until the synchronization behind the set masks below)
+        SP_HIP(ctx, hipMemcpyAsync(A0 + o_cso, h_cso.data(), h_cso.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+        if (!h_cs.empty()) SP_HIP(ctx, hipMemcpyAsync(A0 + o_csl, h_cs.data(), h_cs.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    }
     SP_HIP(ctx, hipMemsetAsync(bnd, 0, (size_t)C * (size_t)(R + 1) * 4, ctx->stream));
     {
         int64_t gx = (longest + 255) / 256;
@@ -1835,7 +2242,18 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
         A.row_counts = (uint32_t *)(S0 + 2 * al(row_cap * 8) + al(row_cap * 4));
         SP_HIP(ctx, hipMemsetAsync(A.row_keys, 0xff, row_cap * 8, ctx->stream));
         SP_HIP(ctx, hipMemsetAsync(small, 0, 64, ctx->stream));
-        {
+        if (wide) {
+            int64_t grid = R;
+            if (grid > (int64_t)ctx->n_cu * 16) grid = (int64_t)ctx->n_cu * 16;
+            sps_wide_args W;
+            W.cset_off = (const int32_t *)(A0 + o_cso);
+            W.cset = (const int32_t *)(A0 + o_csl);
+            W.generic = (getenv("SP_JOIN_GENERIC") && atoi(getenv("SP_JOIN_GENERIC"))) ? 1 : 0;     // cross-check switch
+            if (shift <= 31)
+                SP_LAUNCH(ctx, "sps_join_wide", sps_join_wide<uint32_t>, dim3((unsigned)grid), dim3(WJ_THREADS), 0, A, W);
+            else
+                SP_LAUNCH(ctx, "sps_join_wide", sps_join_wide<unsigned long long>, dim3((unsigned)grid), dim3(WJ_THREADS), 0, A, W);
+        } else {
             int64_t grid = R;
             if (grid > (int64_t)ctx->n_cu * 16) grid = (int64_t)ctx->n_cu * 16;
             const size_t row_lds = (size_t)BJ_NR * (size_t)(C | 1) * 4;     // <= 16.3 KiB

@@ -109,7 +109,8 @@ def makeArgparse(argv=None):
         description="Phase subgenomes of an allopolyploid or hybrid based on repetitive kmers "
                     "(MI355X-native k-mer counting / enrichment; modules 1-2 of SubPhaser).\n"
                     "Limits of the dense path (k <= 15): at most 560 chromosomes in the filter, 8 subgenome columns "
-                    "per config line unless -baseline is 1 or -1, 32 subgenomes in the enrichment.")
+                    "per config line unless -baseline is 1 or -1, 32 subgenomes in the enrichment.  Lists (k > 15, or -engine 3): at "
+                    "most 1024 chromosomes in the filter.")
     for title, desc, options in CLI:
         group = parser.add_argument_group(title, desc)
         for flags, kw in options:

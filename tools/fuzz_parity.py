@@ -5,7 +5,7 @@ random k in 1..32, thresholds, engines, label sets, bin / chunk sizes and set st
 Stream mode (round 6): every count runs with 3..7 chains in flight (SP_LANES_DENSE / SP_LANES_SPARSE / SP_LANES forced -- the
 library keeps toy genomes on one stream by default, which is why 250 K iterations never met the round-5 `s3_part1` race), some
 chromosomes are several tiles long, and a second context (tools/gpu_busy.py) competes for the CUs.
-usage: fuzz_parity.py [iterations=200] [seed=0] [streams]"""
+usage: fuzz_parity.py [iterations=200] [seed=0] [streams | wide]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -49,7 +49,10 @@ def _tr(what):
 LANE_VARS = ("SP_LANES_DENSE", "SP_LANES_SPARSE", "SP_LANES", "SP_C2_BATCH")
 
 
-def run(iters, seed, gpu, ora, verbose=True, streams=False):
+def run(iters, seed, gpu, ora, verbose=True, streams=False, wide=False):
+    """wide=True: the list filter above 64 chromosomes (sps_join_wide) instead of the default draw (_run_wide)."""
+    if wide:
+        return _run_wide(iters, seed, gpu, ora, verbose)
     if not streams:
         return _run(iters, seed, gpu, ora, verbose, False)
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
@@ -180,8 +183,95 @@ def _run(iters, seed, gpu, ora, verbose, streams):
     return bad
 
 
+WIDE_MAXC = 1024      # SP_LIST_MAXC of the library
+
+
+def _run_wide(iters, seed, gpu, ora, verbose):
+    """C in 65..WIDE_MAXC short chromosomes (200 b - 3 kb, shared planted repeats so that keys have many entries), k in
+    16..32, random sets (units of 1-3 chromosomes, 2-5 units, singletons among them), baselines and thresholds, with and
+    without SP_JOIN_GENERIC: the filter's counts, rows, totals and histogram against the oracle."""
+    import time
+    rng = np.random.RandomState(seed)
+    bad = 0
+    t0, limit = time.time(), float(os.environ.get("SP_FUZZ_SECONDS", "0"))
+    saved = os.environ.get("SP_JOIN_GENERIC")
+    it = -1
+    try:
+        for it in range(iters):
+            if limit and time.time() - t0 > limit:
+                it -= 1
+                break
+            C = int(rng.randint(65, WIDE_MAXC + 1))
+            k = int(rng.randint(16, 33))
+            lower = int(rng.randint(1, 3))
+            reps = [ALPHA[rng.randint(0, 4, size=int(rng.randint(40, 400)))] for _ in range(int(rng.randint(1, 8)))]
+            seqs = []
+            for c in range(C):
+                s = ALPHA[rng.randint(0, 4, size=int(rng.choice([200, 1000, 3000])))].copy()
+                r = reps[0][:s.size // 2]          # (twice in every chromosome: none is left without k-mers at lower 2)
+                s[:r.size] = r
+                s[s.size // 2:s.size // 2 + r.size] = r
+                for _ in range(int(rng.randint(0, 6))):
+                    r = reps[rng.randint(0, len(reps))][:s.size]
+                    a = int(rng.randint(0, s.size - r.size + 1))
+                    s[a:a + r.size] = r
+                seqs.append(s)
+            perm = rng.permutation(C).tolist()
+            sgs, i = [], 0
+            while i < C:
+                nu = int(rng.choice([1, 2, 2, 3, 4, 5]))
+                units = []
+                for _ in range(nu):
+                    w = int(rng.choice([1, 1, 1, 2, 3]))
+                    if i < C:
+                        units.append(perm[i:i + w])
+                        i += w
+                sgs.append(units)
+            args = (float(rng.choice([1.0, 1.5, 2.0, 3.0])), int(rng.choice([1, -1, 2])), float(rng.choice([1, 3, 20])), 1e9,
+                    float(rng.choice([0.3, 0.5, 1.0])))
+            os.environ["SP_JOIN_GENERIC"] = str(int(rng.randint(0, 2)))
+            tag = "wide it=%d C=%d k=%d L=%d args=%s generic=%s" % (it, C, k, lower, args, os.environ["SP_JOIN_GENERIC"])
+            if os.environ.get("SP_FUZZ_TRACE"):
+                print(tag, file=sys.stderr, flush=True)
+            try:
+                for ctx in (gpu, ora):
+                    ctx.genome_reset(C)
+                    for j, s in enumerate(seqs):
+                        ctx.genome_add(j, s)
+                    ctx.count(k, lower, 0)
+                csr = sets_to_csr(sgs, list(range(C)))
+                res = []
+                for ctx in (gpu, ora):
+                    try:
+                        nu, nr, nh = ctx.filter(*csr, *args)
+                        kk, cc, ff, tt = ctx.filter_fetch(nr)
+                        res.append((nu, nr, nh, kk, cc, ff, tt, np.sort(ctx.filter_hist(nh))))
+                    except ValueError as e:
+                        res.append(("err", str(e)[:40]))
+                if res[0][0] == "err" or res[1][0] == "err":
+                    assert res[0][0] == res[1][0], "filter error mismatch %s %s" % (res[0], res[1])
+                else:
+                    assert res[0][:3] == res[1][:3], "filter counts %s %s" % (res[0][:3], res[1][:3])
+                    for a, b in zip(res[0][3:], res[1][3:]):
+                        assert a.shape == b.shape and (a == b).all(), "filter rows"
+            except AssertionError as e:
+                bad += 1
+                print("MISMATCH", tag, "->", e)
+                if bad >= 5:
+                    break
+    finally:
+        if saved is None:
+            os.environ.pop("SP_JOIN_GENERIC", None)
+        else:
+            os.environ["SP_JOIN_GENERIC"] = saved
+    if verbose:
+        print("fuzz (wide) seed %d: %d iterations, %d mismatches" % (seed, it + 1, bad), flush=True)
+    return bad
+
+
 if __name__ == "__main__":
     n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     sd = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     st = len(sys.argv) > 3 and sys.argv[3] == "streams"
-    sys.exit(1 if run(n_it, sd, _native.Context(0), OracleContext(nthreads=4), streams=st) else 0)
+    wd = len(sys.argv) > 3 and sys.argv[3] == "wide"
+    sys.exit(1 if run(n_it, sd, _native.Context(0), OracleContext(nthreads=4), streams=st, wide=wd) else 0)
