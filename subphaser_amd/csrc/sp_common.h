@@ -34,7 +34,11 @@ struct sp_chrom {
                                       // the packing of the chromosomes after it
 };
 #define SP_PAD_WORDS 8
-#define SP_LIST_MAXC 1024    // chromosomes the list filter takes (k > 15, count engine 3): sps_join_wide above 64
+#define SP_LIST_MAXC 1024    // chromosomes the list filter takes (k > 15, count engine 3): sps_join_wide above 64; at k <= 15
+                             // list mode takes more, of which at most SP_LIST_MAXC set chromosomes (sps_filter_passengers)
+#define SP_TABLE_LDS (140 * 1024)      // LDS bytes the byte-table filter stages a tile of C rows in (sp_filter.hip),
+#define SP_TABLE_MIN_TILE 256          // at this many slots a tile at least:
+#define SP_TABLE_MAXC (SP_TABLE_LDS / SP_TABLE_MIN_TILE)   // 560 chromosomes; a whole-genome engine-0 count keeps more as lists
 #ifndef SP_DERIVE_PM
 #define SP_DERIVE_PM 1      // the MSB-first packed stream is derived in registers instead of stored (sp_device.h)
 #endif

@@ -421,21 +421,27 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     // (slot, count >= lower) pairs in ascending slot order instead (engine 3: the same partition chain ending in
     // c2_count_list), joined by the list filter.  Measured per pass: Arabidopsis-like 13.0 -> 6.3 ms, peanut-like
     // 35.8 -> 31.6 ms; a wheat-like chromosome (670 Mb: more k-mers than slots) stays on byte tables.
-    // Whole-genome calls on library-owned tables only (the multi-GPU table exchange needs the byte tables).
+    // Whole-genome calls on library-owned tables only (the multi-GPU table exchange needs the byte tables).  Above
+    // SP_TABLE_MAXC chromosomes the byte-table filter cannot run, so engine 0 keeps lists whatever the occupancy; the list
+    // filter takes any number of chromosomes here (sps_filter_passengers above SP_LIST_MAXC).
     bool list_mode = false;
     {
         const char *env3 = getenv("SP_LIST_ENGINE");      // "0": never, "1": whenever possible (tests)
         bool whole = first == 0 && last == (int)ctx->chroms.size();
-        bool possible = whole && sp_engine2_supported(nslots) && ctx->chroms.size() <= SP_LIST_MAXC;
+        bool possible = whole && sp_engine2_supported(nslots);
+        bool external = false;
         int64_t longest = 0;
         for (auto &c : ctx->chroms) {
-            possible = possible && !c.tab_external;
+            external = external || c.tab_external;
             longest = c.len > longest ? c.len : longest;
         }
+        possible = possible && !external;
         if (engine == 3) {
             if (!possible)
-                return sp_fail(ctx, SP_EUNSUP, "count engine 3 (lists) needs k with 2^17..2^31 dense slots, a whole-genome call, "
-                                               "library-owned tables and at most %d chromosomes", SP_LIST_MAXC);
+                return sp_fail(ctx, SP_EUNSUP, "count engine 3 (lists) needs k with 2^17..2^31 dense slots, a whole-genome call "
+                                               "and library-owned tables");
+            list_mode = true;
+        } else if (engine == 0 && possible && ctx->chroms.size() > SP_TABLE_MAXC) {
             list_mode = true;
         } else if (engine == 0 && possible && ctx->chroms.size() <= 64) {     // (the automatic choice: sps_join_blk's lists)
             list_mode = (env3 && env3[0] == '1') || (!(env3 && env3[0] == '0') && longest > 0 && longest * 3 < nslots);

@@ -1683,6 +1683,36 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
     const size_t total = al((size_t)n * sizeof(c2_bdesc)) + (size_t)n * head_bytes + body_total;
     void *&d_ws2 = ctx->lane ? ctx->lane->d_ws2 : ctx->d_ws2;           // this lane's workspace (sp_common.h)
     int64_t &ws2_bytes = ctx->lane ? ctx->lane->ws2_bytes : ctx->ws2_bytes;
+    {   // Every chromosome's workspace carries fixed slack per bucket (~0.8 GB at k = 15, whatever its length): hundreds of
+        // short chromosomes (unanchored scaffolds) do not fit at once.  Only a batch above what the device has free (less a
+        // sixteenth, as the lanes reckon) is split: it runs as consecutive sub-batches on this stream of at most
+        // C2_SPLIT_BYTES each (one chromosome at least) -- a workspace of that size stays with the context, not one that
+        // fills the device.  A batch that fits runs as one, as before.
+        const int64_t C2_SPLIT_BYTES = 8LL << 30;
+        size_t free_b = 0, total_b = 0;
+        const int64_t avail = hipMemGetInfo(&free_b, &total_b) == hipSuccess
+                                  ? (int64_t)free_b + ws2_bytes - (int64_t)(total_b / 16) : (int64_t)total;
+        if (n > 1 && (int64_t)total > avail) {
+            const int64_t budget = avail < C2_SPLIT_BYTES ? avail : C2_SPLIT_BYTES;
+            for (int i0 = 0; i0 < n;) {
+                int64_t acc = (int64_t)al(sizeof(c2_bdesc));
+                int i1 = i0;
+                while (i1 < n) {
+                    const int64_t per = (int64_t)(al(sizeof(c2_bdesc)) + head_bytes +
+                                                  ((i1 + 1 < n ? body_off[(size_t)i1 + 1] : body_total) - body_off[(size_t)i1]));
+                    if (i1 > i0 && acc + per > budget) break;
+                    acc += per;
+                    i1++;
+                }
+                // (the page-locked descriptor buffer below is reused: the previous sub-batch's copy must have left it)
+                if (i0) SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                const int rc = sp_count_engine3_batch(ctx, chrom_idx + i0, i1 - i0, kp, lower, d_len);
+                if (rc) return rc;
+                i0 = i1;
+            }
+            return SP_OK;
+        }
+    }
     if ((int64_t)total > ws2_bytes) {
         if (d_ws2) {
             SP_HIP(ctx, hipStreamSynchronize(ctx->stream));

@@ -628,6 +628,9 @@ extern "C" {
 int sp_filter_view(sp_ctx *ctx, int C, const void *const *d_tabs, int64_t slot_base, int64_t nslots_view,
                    const int64_t *lengths, int k, int lower_count, const void *const *d_ovf, const int64_t *n_ovf) {
     if (!ctx) return SP_EINVAL;
+    if (d_tabs && C > SP_LIST_MAXC)
+        return sp_fail(ctx, SP_EUNSUP, "sp_filter_view: a view takes at most %d chromosomes (got %d); more chromosomes are "
+                                       "filtered on one GPU", SP_LIST_MAXC, C);
     if (d_tabs && (ctx->sparse_mode || ctx->list_mode)) return sp_fail(ctx, SP_EUNSUP, "sp_filter_view: byte-table engines (k <= 15) only");
     if (!d_tabs) {   // back to the local chromosomes
         ctx->fv_on = false;
@@ -716,6 +719,10 @@ int sp_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *un
         if (n_hist) *n_hist = ctx->n_hist;
         return SP_OK;
     }
+    if (C > SP_LIST_MAXC)     // (the byte-table filter stages at most SP_TABLE_MAXC rows)
+        return sp_fail(ctx, SP_EUNSUP, "sp_filter: byte tables of %d chromosomes: more than %d chromosomes are filtered as "
+                                       "lists only -- k = 9..15, a whole-genome count (engine 0 or 3) into library-owned "
+                                       "tables on one GPU; no filter view, bound tables or count engines 1 / 2", C, SP_LIST_MAXC);
     const int64_t nslots = filter_nslots(ctx);
     const int64_t nblk = (nslots + F_SLOTS_PER_BLOCK - 1) / F_SLOTS_PER_BLOCK;
     const int64_t ngroups = (nslots + 63) / 64;
@@ -779,9 +786,9 @@ int sp_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *un
     P.slot_base = filter_base(ctx);
     // LDS tile: the largest power of two of slots whose C byte rows fit 48 KiB (three blocks per CU)
     int TS = F_SLOTS_PER_BLOCK;
-    while (TS > 256 && (size_t)C * TS > F_TILE_BYTES) TS >>= 1;
-    if ((size_t)C * TS > 140 * 1024)
-        return sp_fail(ctx, SP_EUNSUP, "sp_filter: %d chromosomes exceed the LDS staging budget (at most 560)", C);
+    while (TS > SP_TABLE_MIN_TILE && (size_t)C * TS > F_TILE_BYTES) TS >>= 1;
+    if ((size_t)C * TS > SP_TABLE_LDS)
+        return sp_fail(ctx, SP_EUNSUP, "sp_filter: %d chromosomes exceed the LDS staging budget (at most %d)", C, SP_TABLE_MAXC);
     P.TS = TS;
     P.n_multi = n_sets - n_single;
     P.need_hist = 0;    // smallest include with !(include / _all < ratio): the quotient is monotone in include
@@ -824,9 +831,10 @@ int sp_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *un
     if (C > F3_CHROM_MASK) return sp_fail(ctx, SP_EUNSUP, "sp_filter: too many chromosomes");
     // LDS tile: the largest power of two of slots whose R byte rows fit the budget (several blocks per CU)
     TS = F_SLOTS_PER_BLOCK;
-    while (TS > 256 && (size_t)P.R * TS > F_TILE_BYTES) TS >>= 1;
-    if ((size_t)P.R * TS > 140 * 1024)
-        return sp_fail(ctx, SP_EUNSUP, "sp_filter: %d chromosome rows exceed the LDS staging budget (at most 560)", P.R);
+    while (TS > SP_TABLE_MIN_TILE && (size_t)P.R * TS > F_TILE_BYTES) TS >>= 1;
+    if ((size_t)P.R * TS > SP_TABLE_LDS)
+        return sp_fail(ctx, SP_EUNSUP, "sp_filter: %d chromosome rows exceed the LDS staging budget (at most %d)", P.R,
+                       SP_TABLE_MAXC);
     P.TS = TS;
     {
         size_t nR = ((size_t)P.R + 7) & ~(size_t)7;   // padded with neutral rows: the unrolled walk reads whole chunks

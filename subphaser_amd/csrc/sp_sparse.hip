@@ -1933,7 +1933,8 @@ sps_place_rows(const unsigned long long *__restrict__ row_keys, const unsigned l
     const unsigned long long pos = row_off[key >> shift] + row_rank[i];
     out_keys[pos] = key;
     out_tot[pos] = row_tot[i];
-    for (int c = 0; c < C; c++) out_counts[pos * (size_t)C + c] = row_counts[i * (size_t)C + c];
+    if (out_counts)      // (phase A of sps_filter_passengers keeps the keys only)
+        for (int c = 0; c < C; c++) out_counts[pos * (size_t)C + c] = row_counts[i * (size_t)C + c];
 }
 
 // fold-passing totals of range r: hist_stage[start of the range ..) -> out[hist_off[r] ..)
@@ -1949,6 +1950,17 @@ sps_place_hist(const unsigned long long *__restrict__ hist_stage, const uint32_t
     for (int c = 0; c < C; c++) src += bnd[(size_t)c * (size_t)(R + 1) + (size_t)r];
     const unsigned long long dst = hist_off[r];
     for (uint32_t j = 0; j < m; j++) out[dst + j] = hist_stage[src + j];
+}
+
+// SP_ENOMEM naming the size when `bytes` do not fit what the device has free (the buffer's own bytes count as free)
+static int sps_fits(sp_ctx *ctx, const sp_buf &b, int64_t bytes, const char *what) {
+    if (bytes <= b.cap) return SP_OK;
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return SP_OK;     // (sp_buf_ensure reports a failed allocation)
+    const double avail = (double)free_b + (double)b.cap;
+    if ((double)bytes + (double)bytes / 8 + 4096 <= avail) return SP_OK;
+    return sp_fail(ctx, SP_ENOMEM, "list filter: %s need %.2f GiB, the device has %.2f GiB free", what,
+                   (double)bytes / (1 << 30), avail / (1 << 30));
 }
 
 static int sps_filter_sort(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off,
@@ -2055,19 +2067,23 @@ static int sps_filter_sort(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
     return SP_OK;
 }
 
+// pick: the chromosomes whose lists are joined, in list order (nullptr: all of them).  sps_filter_passengers' phase A
+// joins the set chromosomes alone, with unit_chrom numbering the picked lists, and keeps its rows as dense slots without
+// their counts.
 static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off,
                            const int32_t *unit_chrom, const std::vector<double> &den, double min_fold, int baseline,
-                           double min_freq, double max_freq, double ratio) {
-    const int C = sps_C(ctx);
+                           double min_freq, double max_freq, double ratio, const std::vector<int> *pick = nullptr) {
+    const int C = pick ? (int)pick->size() : sps_C(ctx);
     if (C > SP_LIST_MAXC)
         return sp_fail(ctx, SP_EUNSUP, "list filter (k > 15, or engine 3): at most %d chromosomes supported (got %d)", SP_LIST_MAXC, C);
     const bool wide = C > SPS_MAXC;      // sps_join_wide; up to 64 lists sps_join_blk
     int64_t total = 0, longest = 0;
     std::vector<sps_list> hl((size_t)C);
     for (int c = 0; c < C; c++) {
-        hl[(size_t)c] = sps_list{sps_keys(ctx, c), sps_cnts(ctx, c), (long long)sps_n(ctx, c)};
-        total += sps_n(ctx, c);
-        longest = sps_n(ctx, c) > longest ? sps_n(ctx, c) : longest;
+        const int cc = pick ? (*pick)[(size_t)c] : c;
+        hl[(size_t)c] = sps_list{sps_keys(ctx, cc), sps_cnts(ctx, cc), (long long)sps_n(ctx, cc)};
+        total += sps_n(ctx, cc);
+        longest = sps_n(ctx, cc) > longest ? sps_n(ctx, cc) : longest;
     }
     ctx->sf_n = total;
     ctx->n_union = ctx->n_rows = ctx->n_hist = 0;
@@ -2212,6 +2228,9 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
             ms++;
         }
         A.screen = ms <= 32 ? 1 : 0;      // (sps_join_blk keeps 32-bit masks)
+        // the screen takes a set the key does not touch for a failed fold test, which min_fold <= 0 breaks (an all-zero
+        // set passes): phase A of sps_filter_passengers does without it then
+        if (pick && !(min_fold > 0)) A.screen = 0;
         SP_HIP(ctx, hipMemcpyAsync(A0 + o_cs, cs.data(), (size_t)C * 8, hipMemcpyHostToDevice, ctx->stream));
         SP_HIP(ctx, hipStreamSynchronize(ctx->stream));     // cs goes out of scope
         A.chrom_sets = (const unsigned long long *)(A0 + o_cs);
@@ -2231,7 +2250,14 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
     unsigned long long h[4] = {0, 0, 0, 0};
     for (int attempt = 0;; attempt++) {
         const size_t row_bytes = 8 + 8 + 4 + (size_t)C * 4;
-        rc = sp_buf_ensure(ctx, ctx->b_sp_c, (int64_t)(al(row_cap * 8) * 2 + al(row_cap * 4) + al(row_cap * (size_t)C * 4) + 64));
+        const int64_t stage_bytes = (int64_t)(al(row_cap * 8) * 2 + al(row_cap * 4) + al(row_cap * (size_t)C * 4) + 64);
+        if (pick) {     // (phase A, frequency bounds open: with min_fold <= 0 every slot of the set chromosomes is a row)
+            char what[160];
+            snprintf(what, sizeof what, "the candidates of the set chromosomes (%llu rows x %d lists x 4 B staged)",
+                     row_cap, C);
+            if ((rc = sps_fits(ctx, ctx->b_sp_c, stage_bytes, what))) return rc;
+        }
+        rc = sp_buf_ensure(ctx, ctx->b_sp_c, stage_bytes);
         if (rc) return rc;
         (void)row_bytes;
         char *S0 = (char *)ctx->b_sp_c.p;
@@ -2289,8 +2315,10 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
     const int64_t M = ctx->n_rows, H = ctx->n_hist;
     rc = sp_buf_ensure(ctx, ctx->b_sf_keys, (M + 1) * 8);
     if (rc) return rc;
-    rc = sp_buf_ensure(ctx, ctx->b_sf_counts, (M + 1) * (int64_t)C * 4);
-    if (rc) return rc;
+    if (!pick) {
+        rc = sp_buf_ensure(ctx, ctx->b_sf_counts, (M + 1) * (int64_t)C * 4);
+        if (rc) return rc;
+    }
     rc = sp_buf_ensure(ctx, ctx->b_sf_tot, (M + 1) * 8);
     if (rc) return rc;
     rc = sp_buf_ensure(ctx, ctx->b_sf_hist, (H + 1) * 8);
@@ -2299,12 +2327,13 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
         SP_LAUNCH(ctx, "sps_place_rows", sps_place_rows, dim3((unsigned)((h[1] + 255) / 256)), dim3(256), 0,
                   (const unsigned long long *)A.row_keys, (const unsigned long long *)A.row_tot, (const uint32_t *)A.row_rank,
                   (const uint32_t *)A.row_counts, h[1], C, shift, (const unsigned long long *)row_off,
-                  (unsigned long long *)ctx->b_sf_keys.p, (uint32_t *)ctx->b_sf_counts.p, (unsigned long long *)ctx->b_sf_tot.p);
+                  (unsigned long long *)ctx->b_sf_keys.p, pick ? (uint32_t *)nullptr : (uint32_t *)ctx->b_sf_counts.p,
+                  (unsigned long long *)ctx->b_sf_tot.p);
     if (H)
         SP_LAUNCH(ctx, "sps_place_hist", sps_place_hist, dim3((unsigned)((R + 255) / 256)), dim3(256), 0,
                   (const unsigned long long *)A.hist_stage, (const uint32_t *)bnd, C, R, (const uint32_t *)n_hist,
                   (const unsigned long long *)hist_off, (unsigned long long *)ctx->b_sf_hist.p);
-    if (M && ctx->list_mode)
+    if (M && ctx->list_mode && !pick)
         SP_LAUNCH(ctx, "sps_slots_to_keys", sps_slots_to_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0,
                   (unsigned long long *)ctx->b_sf_keys.p, M, sp_make_kparams(ctx->k));
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -2312,13 +2341,373 @@ static int sps_filter_join(sp_ctx *ctx, int n_sets, const int32_t *set_off, cons
     return SP_OK;
 }
 
-// SP_LIST_FILTER=sort selects the first implementation (concatenate + library radix sort), kept as a cross-check
+// ------------------------------------------------------------------ list filter with passengers (k <= 15, C > SP_LIST_MAXC)
+// Set chromosomes (named by a set of two or more units) decide; every other chromosome -- a singleton config line, or
+// through the C-ABI a chromosome in no set: a "passenger" -- only adds to a k-mer's tot and its row.
+//   phase A  sps_filter_join over the set chromosomes' lists alone (sps_join_blk / sps_join_wide, frequency bounds open):
+//            its rows are the slots that pass the fold and ratio tests, ascending.  Exact: sp_filter_decide reads the set
+//            chromosomes only.  A slot that no set chromosome holds is decided like an all-zero row (sps_sg_zero).
+//   phase B  bitmaps over the dense slot space (2^(2k-1) bits: 64 MiB at k = 15), a few streaming passes:
+//     sps_sg_mark     every entry of every list -> union bits U (+ bits H of the set chromosomes' entries when an all-zero
+//                     row passes); 32-bit atomic ORs, one per run of a thread's entries in the same 32-slot word
+//     sps_sg_cand     phase A's slots -> candidate bits X
+//     sps_sg_sums     X |= U & ~H (all-zero row passes); popcounts of X and U per block of words
+//     sps_sg_dir      rank directory D[w] = candidates in the words before w; candidate index -> slot
+//     sps_sg_tot      every entry on a candidate slot: tot[rank] += count (64-bit atomics; tot is the hist)
+//     sps_sg_rows / sps_sg_place   row iff !(tot < min_freq || tot > max_freq) (:645-646), scan -> keys, tot, row index
+//     sps_sg_scatter  every entry on a row slot -> counts[row][chromosome] (zeroed rows, plain stores)
+#define SG_BLOCK 256
+#define SG_PER 16                      // entries (bitmap words) per thread
+#define SG_SPAN (SG_BLOCK * SG_PER)    // entries of one list per workgroup ("chunk"); 64-bit words per workgroup
+
+__global__ void __launch_bounds__(64)
+sps_sg_zero(sp_fsets F, int *__restrict__ out) {
+    if (threadIdx.x) return;
+    bool is_row, is_hist;
+    sp_filter_decide([](int) -> uint32_t { return 0u; }, 0ULL, F, is_row, is_hist);
+    out[0] = is_hist ? 1 : 0;
+}
+
+// a workgroup per chunk (list, first entry); a thread walks SG_PER consecutive entries of the sorted list
+template <bool HELD>
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_mark(const sps_list *__restrict__ lists, const uint2 *__restrict__ chunks, const uint8_t *__restrict__ is_set,
+            uint32_t *__restrict__ U, uint32_t *__restrict__ H) {
+    const uint2 ch = chunks[blockIdx.x];
+    const sps_list L = lists[ch.x];
+    const long long lo = (long long)ch.y + (long long)threadIdx.x * SG_PER;
+    const long long hi = lo + SG_PER < L.n ? lo + SG_PER : L.n;
+    const bool held = HELD && is_set[ch.x];
+    uint32_t wp = 0, bits = 0;
+    for (long long i = lo; i < hi; i++) {
+        const uint32_t s = (uint32_t)L.keys[i], w = s >> 5;
+        if (bits && w != wp) {
+            atomicOr(&U[wp], bits);
+            if (held) atomicOr(&H[wp], bits);
+            bits = 0;
+        }
+        wp = w;
+        bits |= 1u << (s & 31);
+    }
+    if (bits) {
+        atomicOr(&U[wp], bits);
+        if (held) atomicOr(&H[wp], bits);
+    }
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_cand(const unsigned long long *__restrict__ slots, int64_t n, uint32_t *__restrict__ X) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const uint32_t s = (uint32_t)slots[i];
+    atomicOr(&X[s >> 5], 1u << (s & 31));
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_sums(const unsigned long long *__restrict__ U, const unsigned long long *__restrict__ H,
+            unsigned long long *__restrict__ X, int64_t W, int zero_pass, unsigned long long *__restrict__ bsum_x,
+            unsigned long long *__restrict__ bsum_u) {
+    __shared__ unsigned long long red[16];
+    const int64_t w0 = (int64_t)blockIdx.x * SG_SPAN;
+    unsigned long long nx = 0, nu = 0;
+    for (int j = 0; j < SG_PER; j++) {
+        const int64_t w = w0 + (int64_t)j * SG_BLOCK + threadIdx.x;
+        if (w >= W) break;
+        const unsigned long long u = U[w];
+        unsigned long long x = X[w];
+        if (zero_pass) {
+            x |= u & ~H[w];
+            X[w] = x;
+        }
+        nx += (unsigned long long)__popcll(x);
+        nu += (unsigned long long)__popcll(u);
+    }
+    const unsigned long long tx = sp_block_sum_u64(nx, red);
+    const unsigned long long tu = sp_block_sum_u64(nu, red);
+    if (threadIdx.x == 0) {
+        bsum_x[blockIdx.x] = tx;
+        bsum_u[blockIdx.x] = tu;
+    }
+}
+
+// D[w] and the slots of the candidates; a thread owns SG_PER consecutive words (the order of the ranks)
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_dir(const unsigned long long *__restrict__ X, int64_t W, const unsigned long long *__restrict__ boff,
+           uint32_t *__restrict__ D, uint32_t *__restrict__ slot_of) {
+    __shared__ unsigned long long wsum[16];
+    const int64_t t0 = (int64_t)blockIdx.x * SG_SPAN + (int64_t)threadIdx.x * SG_PER;
+    unsigned long long s = 0;
+    for (int j = 0; j < SG_PER; j++)
+        if (t0 + j < W) s += (unsigned long long)__popcll(X[t0 + j]);
+    unsigned long long tot;
+    unsigned long long run = boff[blockIdx.x] + sp_block_excl_scan(s, wsum, tot);
+    for (int j = 0; j < SG_PER; j++) {
+        const int64_t w = t0 + j;
+        if (w >= W) break;
+        D[w] = (uint32_t)run;
+        for (unsigned long long x = X[w]; x; x &= x - 1) slot_of[run++] = (uint32_t)((w << 6) + __builtin_ctzll(x));
+    }
+}
+
+// rank of slot s among the candidates, or -1
+__device__ __forceinline__ long long sg_rank(const unsigned long long *__restrict__ X, const uint32_t *__restrict__ D,
+                                             uint32_t s) {
+    const unsigned long long x = X[s >> 6], b = 1ULL << (s & 63);
+    return (x & b) ? (long long)D[s >> 6] + __popcll(x & (b - 1)) : -1LL;
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_tot(const sps_list *__restrict__ lists, const uint2 *__restrict__ chunks, const unsigned long long *__restrict__ X,
+           const uint32_t *__restrict__ D, unsigned long long *__restrict__ tot) {
+    const uint2 ch = chunks[blockIdx.x];
+    const sps_list L = lists[ch.x];
+    const long long lo = (long long)ch.y + (long long)threadIdx.x * SG_PER;
+    const long long hi = lo + SG_PER < L.n ? lo + SG_PER : L.n;
+    for (long long i = lo; i < hi; i++) {
+        const long long r = sg_rank(X, D, (uint32_t)L.keys[i]);
+        if (r >= 0) atomicAdd(&tot[r], (unsigned long long)L.cnts[i]);
+    }
+}
+
+__device__ __forceinline__ bool sg_is_row(unsigned long long tot, double min_freq, double max_freq) {
+    const double t = (double)tot;
+    return !(t < min_freq || t > max_freq);      // :645-646
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_rows(const unsigned long long *__restrict__ tot, int64_t n, double min_freq, double max_freq,
+            unsigned long long *__restrict__ bsum) {
+    __shared__ unsigned long long red[16];
+    const int64_t i0 = (int64_t)blockIdx.x * SG_SPAN;
+    unsigned long long c = 0;
+    for (int j = 0; j < SG_PER; j++) {
+        const int64_t i = i0 + (int64_t)j * SG_BLOCK + threadIdx.x;
+        if (i < n && sg_is_row(tot[i], min_freq, max_freq)) c++;
+    }
+    const unsigned long long t = sp_block_sum_u64(c, red);
+    if (threadIdx.x == 0) bsum[blockIdx.x] = t;
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_place(const unsigned long long *__restrict__ tot, const uint32_t *__restrict__ slot_of, int64_t n, double min_freq,
+             double max_freq, const unsigned long long *__restrict__ boff, uint32_t *__restrict__ row_of,
+             unsigned long long *__restrict__ out_keys, unsigned long long *__restrict__ out_tot) {
+    __shared__ uint32_t lds[16];
+    const int64_t i0 = (int64_t)blockIdx.x * SG_SPAN;
+    unsigned long long off = boff[blockIdx.x];
+    for (int j = 0; j < SG_PER; j++) {
+        const int64_t i = i0 + (int64_t)j * SG_BLOCK + threadIdx.x;
+        const unsigned long long t = i < n ? tot[i] : 0ULL;
+        const bool p = i < n && sg_is_row(t, min_freq, max_freq);
+        uint32_t nblk;
+        const uint32_t my = sp_block_excl_count(p, lds, nblk);
+        if (i < n) row_of[i] = p ? (uint32_t)(off + my) : 0xffffffffu;
+        if (p) {
+            out_keys[off + my] = slot_of[i];
+            out_tot[off + my] = t;
+        }
+        off += nblk;
+    }
+}
+
+__global__ void __launch_bounds__(SG_BLOCK)
+sps_sg_scatter(const sps_list *__restrict__ lists, const uint2 *__restrict__ chunks, const unsigned long long *__restrict__ X,
+               const uint32_t *__restrict__ D, const uint32_t *__restrict__ row_of, int C, uint32_t *__restrict__ counts) {
+    const uint2 ch = chunks[blockIdx.x];
+    const sps_list L = lists[ch.x];
+    const long long lo = (long long)ch.y + (long long)threadIdx.x * SG_PER;
+    const long long hi = lo + SG_PER < L.n ? lo + SG_PER : L.n;
+    for (long long i = lo; i < hi; i++) {
+        const long long r = sg_rank(X, D, (uint32_t)L.keys[i]);
+        if (r < 0) continue;
+        const uint32_t row = row_of[r];
+        if (row != 0xffffffffu) counts[(size_t)row * (size_t)C + ch.x] = L.cnts[i];
+    }
+}
+
+static int sps_filter_passengers(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off,
+                                 const int32_t *unit_chrom, const std::vector<double> &den, double min_fold, int baseline,
+                                 double min_freq, double max_freq, double ratio) {
+    const int C = sps_C(ctx);
+    const int n_units = set_off[n_sets];
+    // ---- phase A: the set chromosomes, renumbered in ascending order; the sets of one unit left out
+    std::vector<int> pick, num((size_t)C, -1);
+    for (int st = 0; st < n_sets; st++)
+        if (set_off[st + 1] - set_off[st] > 1)
+            for (int j = unit_off[set_off[st]]; j < unit_off[set_off[st + 1]]; j++) num[(size_t)unit_chrom[j]] = 0;
+    for (int c = 0; c < C; c++)
+        if (num[(size_t)c] == 0) {
+            num[(size_t)c] = (int)pick.size();
+            pick.push_back(c);
+        }
+    if ((int)pick.size() > SP_LIST_MAXC)
+        return sp_fail(ctx, SP_EUNSUP, "list filter: at most %d set chromosomes (chromosomes named by a set of two or more "
+                                       "units) supported (got %d of %d chromosomes)", SP_LIST_MAXC, (int)pick.size(), C);
+    std::vector<int32_t> a_so(1, 0), a_uo(1, 0), a_uc;
+    std::vector<double> a_den, a_inv;
+    for (int st = 0; st < n_sets; st++) {
+        if (set_off[st + 1] - set_off[st] <= 1) continue;
+        for (int u = set_off[st]; u < set_off[st + 1]; u++) {
+            for (int j = unit_off[u]; j < unit_off[u + 1]; j++) a_uc.push_back(num[(size_t)unit_chrom[j]]);
+            a_uo.push_back((int32_t)a_uc.size());
+            a_den.push_back(den[(size_t)u]);
+            a_inv.push_back(den[(size_t)(n_units + u)]);
+        }
+        a_so.push_back((int32_t)a_den.size());
+    }
+    a_den.insert(a_den.end(), a_inv.begin(), a_inv.end());
+    a_uc.push_back(0);      // (never read: keeps .data() valid when every unit is empty)
+    int rc = sps_filter_join(ctx, (int)a_so.size() - 1, a_so.data(), a_uo.data(), a_uc.data(), a_den, min_fold, baseline,
+                             -1.0, HUGE_VAL, ratio, &pick);
+    if (rc) return rc;
+    const int64_t n_a = ctx->n_rows;      // phase A's slots, ascending, in b_sf_keys
+    // ---- phase B
+    int64_t total = 0;
+    std::vector<sps_list> hl((size_t)C);
+    std::vector<uint2> hc;
+    std::vector<uint8_t> hs((size_t)C, 0);
+    for (int c = 0; c < C; c++) {
+        const int64_t n = sps_n(ctx, c);
+        hl[(size_t)c] = sps_list{sps_keys(ctx, c), sps_cnts(ctx, c), (long long)n};
+        hs[(size_t)c] = num[(size_t)c] >= 0;
+        total += n;
+        for (int64_t s = 0; s < n; s += SG_SPAN) hc.push_back(make_uint2((unsigned)c, (unsigned)s));
+    }
+    ctx->sf_n = total;
+    ctx->n_union = ctx->n_rows = ctx->n_hist = 0;
+    ctx->filtered = false;
+    const int64_t W = (ctx->nslots + 63) / 64, nbw = (W + SG_SPAN - 1) / SG_SPAN;
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    // b_sp_a: lists | chunks | set flags | set arrays of sps_sg_zero | block sums of the words (X, U) | small
+    //         ([0] candidates [1] union [2] rows [3] the all-zero decision) | block sums of the candidates
+    const size_t nch = hc.size(), nuc = (size_t)unit_off[n_units];
+    const size_t o_l = 0, o_ch = al((size_t)C * sizeof(sps_list)), o_is = o_ch + al((nch + 1) * sizeof(uint2)),
+                 o_so = o_is + al((size_t)C), o_uo = o_so + al((size_t)(n_sets + 1) * 4),
+                 o_uc = o_uo + al((size_t)(n_units + 1) * 4), o_den = o_uc + al((nuc + 1) * 4),
+                 o_bx = o_den + al((size_t)n_units * 16), o_bu = o_bx + al((size_t)(nbw + 1) * 8),
+                 o_small = o_bu + al((size_t)(nbw + 1) * 8), o_br = o_small + 256;
+    // b_sp_b: U | X | H | D
+    const size_t o_X = al((size_t)W * 8), o_H = 2 * o_X, o_D = 3 * o_X, b_bytes = o_D + al((size_t)W * 4);
+    if ((rc = sps_fits(ctx, ctx->b_sp_b, (int64_t)b_bytes, "the slot bitmaps and their rank directory"))) return rc;
+    if ((rc = sp_buf_ensure(ctx, ctx->b_sp_b, (int64_t)b_bytes))) return rc;
+    // (the candidates' block sums: room for every slot being one)
+    const size_t a_bytes = o_br + al((size_t)(ctx->nslots / SG_SPAN + 2) * 8);
+    if ((rc = sp_buf_ensure(ctx, ctx->b_sp_a, (int64_t)a_bytes))) return rc;
+    char *A0 = (char *)ctx->b_sp_a.p, *B0 = (char *)ctx->b_sp_b.p;
+    const sps_list *d_l = (const sps_list *)(A0 + o_l);
+    const uint2 *d_ch = (const uint2 *)(A0 + o_ch);
+    unsigned long long *bx = (unsigned long long *)(A0 + o_bx), *bu = (unsigned long long *)(A0 + o_bu),
+                       *small = (unsigned long long *)(A0 + o_small), *br = (unsigned long long *)(A0 + o_br);
+    unsigned long long *U = (unsigned long long *)B0, *X = (unsigned long long *)(B0 + o_X),
+                       *H = (unsigned long long *)(B0 + o_H);
+    uint32_t *D = (uint32_t *)(B0 + o_D);
+    SP_HIP(ctx, hipMemcpyAsync(A0 + o_l, hl.data(), (size_t)C * sizeof(sps_list), hipMemcpyHostToDevice, ctx->stream));
+    if (nch) SP_HIP(ctx, hipMemcpyAsync(A0 + o_ch, hc.data(), nch * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(A0 + o_is, hs.data(), (size_t)C, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(A0 + o_so, set_off, (size_t)(n_sets + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(A0 + o_uo, unit_off, (size_t)(n_units + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (nuc) SP_HIP(ctx, hipMemcpyAsync(A0 + o_uc, unit_chrom, nuc * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(A0 + o_den, den.data(), (size_t)n_units * 16, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemsetAsync(small, 0, 256, ctx->stream));
+    sp_fsets F;
+    F.n_sets = n_sets;
+    F.n_multi = 0;
+    for (int st = 0; st < n_sets; st++) F.n_multi += (set_off[st + 1] - set_off[st]) > 1;
+    F.baseline = baseline;
+    F.set_off = (const int32_t *)(A0 + o_so);
+    F.unit_off = (const int32_t *)(A0 + o_uo);
+    F.unit_chrom = (const int32_t *)(A0 + o_uc);
+    F.unit_den = (const double *)(A0 + o_den);
+    F.unit_inv = F.unit_den + n_units;
+    F.min_fold = min_fold;
+    F.min_freq = min_freq;
+    F.max_freq = max_freq;
+    F.ratio = ratio;
+    SP_LAUNCH(ctx, "sps_sg_zero", sps_sg_zero, dim3(1), dim3(64), 0, F, (int *)(small + 3));
+    unsigned long long h[4] = {0, 0, 0, 0};
+    SP_HIP(ctx, hipMemcpyAsync(h, small, 32, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));     // (the host vectors go out of scope)
+    const int zero_pass = (int)(h[3] & 1);
+    SP_HIP(ctx, hipMemsetAsync(B0, 0, zero_pass ? o_D : o_H, ctx->stream));     // U, X (, H)
+    if (nch) {
+        if (zero_pass)
+            SP_LAUNCH(ctx, "sps_sg_mark", sps_sg_mark<true>, dim3((unsigned)nch), dim3(SG_BLOCK), 0, d_l, d_ch,
+                      (const uint8_t *)(A0 + o_is), (uint32_t *)U, (uint32_t *)H);
+        else
+            SP_LAUNCH(ctx, "sps_sg_mark", sps_sg_mark<false>, dim3((unsigned)nch), dim3(SG_BLOCK), 0, d_l, d_ch,
+                      (const uint8_t *)(A0 + o_is), (uint32_t *)U, (uint32_t *)nullptr);
+    }
+    if (n_a)
+        SP_LAUNCH(ctx, "sps_sg_cand", sps_sg_cand, dim3((unsigned)((n_a + SG_BLOCK - 1) / SG_BLOCK)), dim3(SG_BLOCK), 0,
+                  (const unsigned long long *)ctx->b_sf_keys.p, n_a, (uint32_t *)X);
+    SP_LAUNCH(ctx, "sps_sg_sums", sps_sg_sums, dim3((unsigned)nbw), dim3(SG_BLOCK), 0, (const unsigned long long *)U,
+              (const unsigned long long *)H, X, W, zero_pass, bx, bu);
+    SP_LAUNCH(ctx, "scan_excl_u64", scan_excl_u64, dim3(1), dim3(1024), 0, bx, nbw, small);
+    SP_LAUNCH(ctx, "scan_excl_u64", scan_excl_u64, dim3(1), dim3(1024), 0, bu, nbw, small + 1);
+    SP_HIP(ctx, hipMemcpyAsync(h, small, 16, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    const int64_t n_cand = (int64_t)h[0];
+    ctx->n_union = (int64_t)h[1];
+    // b_sp_c: slot of every candidate | row index of every candidate; b_sf_hist: the candidates' tot (= the hist)
+    const size_t o_row = al((size_t)(n_cand + 1) * 4), c_bytes = 2 * o_row;
+    if ((rc = sps_fits(ctx, ctx->b_sp_c, (int64_t)c_bytes, "the candidates' slots and row indices"))) return rc;
+    if ((rc = sp_buf_ensure(ctx, ctx->b_sp_c, (int64_t)c_bytes))) return rc;
+    if ((rc = sps_fits(ctx, ctx->b_sf_hist, (n_cand + 1) * 8, "the candidates' totals"))) return rc;
+    if ((rc = sp_buf_ensure(ctx, ctx->b_sf_hist, (n_cand + 1) * 8))) return rc;
+    uint32_t *slot_of = (uint32_t *)ctx->b_sp_c.p, *row_of = (uint32_t *)((char *)ctx->b_sp_c.p + o_row);
+    unsigned long long *tot = (unsigned long long *)ctx->b_sf_hist.p;
+    SP_LAUNCH(ctx, "sps_sg_dir", sps_sg_dir, dim3((unsigned)nbw), dim3(SG_BLOCK), 0, (const unsigned long long *)X, W,
+              (const unsigned long long *)bx, D, slot_of);
+    int64_t M = 0;
+    if (n_cand) {
+        SP_HIP(ctx, hipMemsetAsync(tot, 0, (size_t)n_cand * 8, ctx->stream));
+        SP_LAUNCH(ctx, "sps_sg_tot", sps_sg_tot, dim3((unsigned)nch), dim3(SG_BLOCK), 0, d_l, d_ch,
+                  (const unsigned long long *)X, (const uint32_t *)D, tot);
+        // rows: the candidates whose tot lies within the bounds, in slot order
+        const int64_t nbc = (n_cand + SG_SPAN - 1) / SG_SPAN;      // <= nslots / SG_SPAN + 1
+        SP_LAUNCH(ctx, "sps_sg_rows", sps_sg_rows, dim3((unsigned)nbc), dim3(SG_BLOCK), 0, (const unsigned long long *)tot,
+                  n_cand, min_freq, max_freq, br);
+        SP_LAUNCH(ctx, "scan_excl_u64", scan_excl_u64, dim3(1), dim3(1024), 0, br, nbc, small + 2);
+        SP_HIP(ctx, hipMemcpyAsync(h + 2, small + 2, 8, hipMemcpyDeviceToHost, ctx->stream));
+        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        M = (int64_t)h[2];
+        const int64_t cnt_bytes = (M + 1) * (int64_t)C * 4;
+        char what[128];
+        snprintf(what, sizeof what, "the rows (%lld rows x %d chromosomes x 4 B)", (long long)M, C);
+        if ((rc = sps_fits(ctx, ctx->b_sf_counts, cnt_bytes, what))) return rc;
+        if ((rc = sp_buf_ensure(ctx, ctx->b_sf_keys, (M + 1) * 8))) return rc;
+        if ((rc = sp_buf_ensure(ctx, ctx->b_sf_tot, (M + 1) * 8))) return rc;
+        if ((rc = sp_buf_ensure(ctx, ctx->b_sf_counts, cnt_bytes))) return rc;
+        SP_LAUNCH(ctx, "sps_sg_place", sps_sg_place, dim3((unsigned)nbc), dim3(SG_BLOCK), 0, (const unsigned long long *)tot,
+                  (const uint32_t *)slot_of, n_cand, min_freq, max_freq, (const unsigned long long *)br, row_of,
+                  (unsigned long long *)ctx->b_sf_keys.p, (unsigned long long *)ctx->b_sf_tot.p);
+        if (M) {
+            SP_HIP(ctx, hipMemsetAsync(ctx->b_sf_counts.p, 0, (size_t)M * (size_t)C * 4, ctx->stream));
+            SP_LAUNCH(ctx, "sps_sg_scatter", sps_sg_scatter, dim3((unsigned)nch), dim3(SG_BLOCK), 0, d_l, d_ch,
+                      (const unsigned long long *)X, (const uint32_t *)D, (const uint32_t *)row_of, C,
+                      (uint32_t *)ctx->b_sf_counts.p);
+            SP_LAUNCH(ctx, "sps_slots_to_keys", sps_slots_to_keys, dim3((unsigned)((M + 255) / 256)), dim3(256), 0,
+                      (unsigned long long *)ctx->b_sf_keys.p, M, sp_make_kparams(ctx->k));
+        }
+    }
+    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    ctx->n_rows = M;
+    ctx->n_hist = n_cand;
+    ctx->filtered = true;
+    return SP_OK;
+}
+
+// SP_LIST_FILTER=sort selects the first implementation (concatenate + library radix sort), kept as a cross-check; list
+// mode (k <= 15) above SP_LIST_MAXC chromosomes filters in two phases (sps_filter_passengers)
 int sp_sparse_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off,
                      const int32_t *unit_chrom, const std::vector<double> &den, double min_fold, int baseline,
                      double min_freq, double max_freq, double ratio) {
     const char *e = getenv("SP_LIST_FILTER");
     if (e && !strcmp(e, "sort"))
         return sps_filter_sort(ctx, n_sets, set_off, unit_off, unit_chrom, den, min_fold, baseline, min_freq, max_freq, ratio);
+    if (ctx->list_mode && !ctx->sv_on && sps_C(ctx) > SP_LIST_MAXC)
+        return sps_filter_passengers(ctx, n_sets, set_off, unit_off, unit_chrom, den, min_fold, baseline, min_freq, max_freq,
+                                     ratio);
     return sps_filter_join(ctx, n_sets, set_off, unit_off, unit_chrom, den, min_fold, baseline, min_freq, max_freq, ratio);
 }
 
@@ -2703,6 +3092,9 @@ int sp_sparse_view(sp_ctx *ctx, int C, const void *const *d_keys, const void *co
     }
     if (C <= 0 || !d_counts || !n || !lengths || k < 16 || k > 32)
         return sp_fail(ctx, SP_EINVAL, "sp_sparse_view: bad arguments (k = 16..32)");
+    if (C > SP_LIST_MAXC)
+        return sp_fail(ctx, SP_EUNSUP, "sp_sparse_view: a view takes at most %d chromosomes (got %d); more chromosomes are "
+                                       "filtered on one GPU", SP_LIST_MAXC, C);
     if (ctx->fv_on) return sp_fail(ctx, SP_EINVAL, "sp_sparse_view: a dense filter view is active");
     if (ctx->k != 0 && ctx->k != k) return sp_fail(ctx, SP_EINVAL, "sp_sparse_view: k=%d but the context counted with k=%d", k, ctx->k);
     for (int i = 0; i < C; i++)

@@ -108,9 +108,10 @@ def makeArgparse(argv=None):
         prog="subphaser", formatter_class=argparse.RawDescriptionHelpFormatter,
         description="Phase subgenomes of an allopolyploid or hybrid based on repetitive kmers "
                     "(MI355X-native k-mer counting / enrichment; modules 1-2 of SubPhaser).\n"
-                    "Limits of the dense path (k <= 15): at most 560 chromosomes in the filter, 8 subgenome columns "
-                    "per config line unless -baseline is 1 or -1, 32 subgenomes in the enrichment.  Lists (k > 15, or -engine 3): at "
-                    "most 1024 chromosomes in the filter.")
+                    "Limits: 8 subgenome columns per config line unless -baseline is 1 or -1, 32 subgenomes in the "
+                    "enrichment.  k = 9..15: any number of chromosomes (lists above 560), of which at most 1024 on config "
+                    "lines of two or more units; singleton lines only add to the k-mer totals.  k <= 8: at most 560 "
+                    "chromosomes.  k > 15: at most 1024 chromosomes in the filter.")
     for title, desc, options in CLI:
         group = parser.add_argument_group(title, desc)
         for flags, kw in options:

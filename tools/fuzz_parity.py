@@ -5,7 +5,8 @@ random k in 1..32, thresholds, engines, label sets, bin / chunk sizes and set st
 Stream mode (round 6): every count runs with 3..7 chains in flight (SP_LANES_DENSE / SP_LANES_SPARSE / SP_LANES forced -- the
 library keeps toy genomes on one stream by default, which is why 250 K iterations never met the round-5 `s3_part1` race), some
 chromosomes are several tiles long, and a second context (tools/gpu_busy.py) competes for the CUs.
-usage: fuzz_parity.py [iterations=200] [seed=0] [streams | wide]"""
+Singletons mode: k <= 15 above 1024 chromosomes (set chromosomes next to 1025..3000 passengers).
+usage: fuzz_parity.py [iterations=200] [seed=0] [streams | wide | singletons]"""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "oracle")); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -269,9 +270,107 @@ def _run_wide(iters, seed, gpu, ora, verbose):
     return bad
 
 
+def _run_singletons(iters, seed, gpu, ora, verbose):
+    """k <= 15 above WIDE_MAXC chromosomes (sps_filter_passengers): 10-40 core chromosomes (2-10 kb; one draw in four
+    65-120: phase A through sps_join_wide) in random sets next to 1025..3000 passengers (300 b - 3 kb; half of them
+    singleton lines, half in no set), every chromosome with `lower` copies of a planted repeat, k in 9..15 (list mode),
+    random baselines, thresholds, frequency bounds and ratios (min_fold 0 included), with and without SP_JOIN_GENERIC:
+    counts, rows, totals and histogram against the oracle."""
+    import time
+    rng = np.random.RandomState(seed)
+    bad = 0
+    t0, limit = time.time(), float(os.environ.get("SP_FUZZ_SECONDS", "0"))
+    saved = os.environ.get("SP_JOIN_GENERIC")
+    it = -1
+    try:
+        for it in range(iters):
+            if limit and time.time() - t0 > limit:
+                it -= 1
+                break
+            n_core = int(rng.randint(10, 41)) if rng.randint(0, 4) else int(rng.randint(65, 121))
+            C = n_core + int(rng.randint(WIDE_MAXC + 1, 3001))
+            k = int(rng.randint(9, 16))
+            lower = int(rng.randint(2, 4))
+            reps = [ALPHA[rng.randint(0, 4, size=int(rng.randint(40, 91)))] for _ in range(int(rng.randint(2, 40)))]
+            seqs = []
+            for c in range(C):
+                s = ALPHA[rng.randint(0, 4, size=int(rng.randint(2000, 10001) if c < n_core else rng.randint(300, 3001)))].copy()
+                r = reps[int(rng.randint(0, len(reps)))]
+                share = s.size // lower          # (`lower` copies: no chromosome is left without k-mers)
+                for j in range(lower):
+                    a = j * share + int(rng.randint(0, share - r.size + 1))
+                    s[a:a + r.size] = r
+                if c < n_core:
+                    for _ in range(int(rng.randint(0, 6))):
+                        r = reps[rng.randint(0, len(reps))]
+                        a = int(rng.randint(0, s.size - r.size + 1))
+                        s[a:a + r.size] = r
+                seqs.append(s)
+            perm = rng.permutation(n_core).tolist()
+            sgs, i = [], 0
+            while i < n_core:
+                nu = int(rng.choice([1, 2, 2, 3, 4, 5]))
+                units = []
+                for _ in range(nu):
+                    w = int(rng.choice([1, 1, 1, 2, 3]))
+                    if i < n_core:
+                        units.append(perm[i:i + w])
+                        i += w
+                sgs.append(units)
+            if all(len(u) < 2 for u in sgs):
+                sgs.append([[perm[0]], [perm[-1]]])
+            sgs += [[[c]] for c in range(n_core, C) if rng.randint(0, 2)]
+            args = (float(rng.choice([0.0, 1.0, 1.5, 2.0, 3.0])), int(rng.choice([1, -1, 2])), float(rng.choice([1, 3, 20])),
+                    float(rng.choice([1e9, 30, 100])), float(rng.choice([0.05, 0.3, 0.5, 1.0])))
+            os.environ["SP_JOIN_GENERIC"] = str(int(rng.randint(0, 2)))
+            tag = "singletons it=%d C=%d core=%d k=%d L=%d args=%s generic=%s" % (it, C, n_core, k, lower, args,
+                                                                                 os.environ["SP_JOIN_GENERIC"])
+            if os.environ.get("SP_FUZZ_TRACE"):
+                print(tag, file=sys.stderr, flush=True)
+            try:
+                for ctx in (gpu, ora):
+                    ctx.genome_reset(C)
+                    for j, s in enumerate(seqs):
+                        ctx.genome_add(j, s)
+                    ctx.count(k, lower, 0)
+                csr = sets_to_csr(sgs, list(range(C)))
+                res = []
+                for ctx in (gpu, ora):
+                    try:
+                        nu, nr, nh = ctx.filter(*csr, *args)
+                        kk, cc, ff, tt = ctx.filter_fetch(nr)
+                        res.append((nu, nr, nh, kk, cc, ff, tt, np.sort(ctx.filter_hist(nh))))
+                    except ValueError as e:
+                        res.append(("err", str(e)[:40]))
+                if res[0][0] == "err" or res[1][0] == "err":
+                    assert res[0][0] == res[1][0], "filter error mismatch %s %s" % (res[0], res[1])
+                else:
+                    assert res[0][:3] == res[1][:3], "filter counts %s %s" % (res[0][:3], res[1][:3])
+                    for a, b in zip(res[0][3:], res[1][3:]):
+                        assert a.shape == b.shape and (a == b).all(), "filter rows"
+                if verbose and it % 20 == 0:
+                    print("  it=%d C=%d core=%d k=%d union/rows/hist=%s %.0fs" % (it, C, n_core, k, res[1][:3],
+                                                                               time.time() - t0), flush=True)
+            except AssertionError as e:
+                bad += 1
+                print("MISMATCH", tag, "->", e)
+                if bad >= 5:
+                    break
+    finally:
+        if saved is None:
+            os.environ.pop("SP_JOIN_GENERIC", None)
+        else:
+            os.environ["SP_JOIN_GENERIC"] = saved
+    if verbose:
+        print("fuzz (singletons) seed %d: %d iterations, %d mismatches" % (seed, it + 1, bad), flush=True)
+    return bad
+
+
 if __name__ == "__main__":
     n_it = int(sys.argv[1]) if len(sys.argv) > 1 else 200
     sd = int(sys.argv[2]) if len(sys.argv) > 2 else 0
     st = len(sys.argv) > 3 and sys.argv[3] == "streams"
     wd = len(sys.argv) > 3 and sys.argv[3] == "wide"
+    if len(sys.argv) > 3 and sys.argv[3] == "singletons":
+        sys.exit(1 if _run_singletons(n_it, sd, _native.Context(0), OracleContext(nthreads=4), True) else 0)
     sys.exit(1 if run(n_it, sd, _native.Context(0), OracleContext(nthreads=4), streams=st, wide=wd) else 0)
