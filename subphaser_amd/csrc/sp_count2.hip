@@ -24,6 +24,7 @@
 //   0.625 x2 (scans) + 3 w + 3 r + 2 w + 2 r + 1 x slots/base (table write).
 #include "sp_device.h"
 #include "sp_c2batch.h"
+#include "sp_swar.h"
 
 #define C2_B3 15                      // slot bits resolved inside LDS
 #define C2_FINE (1 << C2_B3)          // slots per fine bucket
@@ -245,7 +246,10 @@ __device__ __forceinline__ void c2_tiles_body(const unsigned long long *__restri
 
 // block-wide exclusive scan of hist[0..F) (F <= 256 <= blockDim) -> start[]; returns total
 // LDSB: the two barriers order LDS traffic only (sp_barrier_lds): global stores of the previous tile stay in flight
-template <bool LDSB = false>
+// THREADS: the block size where the caller knows it (0: blockDim.x -- a 2-byte load from the dispatch packet, and the wait for it is a
+// wait for EVERY vector-memory operation in flight: in c2_part1 that was an `s_waitcnt vmcnt(0)` in the middle of the tile, on the
+// prefetched words and on the stores the LDS-only barriers are there to leave alone)
+template <bool LDSB = false, int THREADS = 0>
 __device__ __forceinline__ uint32_t c2_scan_F(const uint32_t *hist, uint32_t *start, int F,
                                               uint32_t *wsum /*>=4*/) {
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
@@ -260,7 +264,8 @@ __device__ __forceinline__ uint32_t c2_scan_F(const uint32_t *hist, uint32_t *st
     if (LDSB) sp_barrier_lds();
     else __syncthreads();
     uint32_t base = 0, total = 0;
-    const int nwv = (int)(blockDim.x >> 6) < 4 ? (int)(blockDim.x >> 6) : 4;
+    const int nwb = THREADS ? THREADS >> 6 : (int)(blockDim.x >> 6);
+    const int nwv = nwb < 4 ? nwb : 4;
     for (int w = 0; w < nwv; w++) {
         uint32_t s = wsum[w];
         if (w < wave) base += s;
@@ -283,6 +288,10 @@ __device__ __forceinline__ uint32_t c2_scan_F(const uint32_t *hist, uint32_t *st
 __device__ __forceinline__ uint32_t c2_pack_lo(uint32_t a, uint32_t b) {   // low halves of a and b
     return __builtin_amdgcn_perm(b, a, 0x05040100u);
 }
+// The parity of k is a tag type (one branch per launch, not one per key; the LDS arrays are declared once, outside), and a wave whose 64 units
+// are all there with all 32 starts valid -- nearly every wave of a genome without N runs -- ranks and scatters its keys without
+// the per-key validity masks (`fast`: decided per wave; no barrier lies inside the two phases it changes).  slot[] holds the
+// LDS record of a key (bucket << 24 | remaining bits) from the scan on: the bucket is formed once per key.
 __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm,
           int64_t n_units /* of 32 starts */, sp_kparams32 kp, int shift1 /* T-B1 */, int F1, int split,
           const unsigned long long *__restrict__ off1, unsigned long long *__restrict__ cursor1, int64_t n_tiles,
@@ -340,6 +349,8 @@ __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, c
 #if C2_P1_ASYNC
     take();
 #endif
+    auto tiles = [&](auto parity) {
+    constexpr bool ODD = decltype(parity)::value;
     for (int64_t tile = blockIdx.x; tile < n_tiles; tile += gridDim.x) {
         if (threadIdx.x < F1) hist[threadIdx.x] = 0;
         const int64_t u = tile * C2_P1_THREADS + threadIdx.x;
@@ -351,18 +362,36 @@ __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, c
         fetch(tile + gridDim.x);
         bar();
         uint32_t slot[32], rank[32], ok = 0;
-        if (u >= n_units) {      // (a thread without a unit: its slots index start[] below, unconditionally -- advisor r05)
-#pragma unroll
-            for (int j = 0; j < 32; j++) slot[j] = 0;
-        }
-        if (u < n_units) {
-            ok = ~(uint32_t)sp_bad_from_words64((uint64_t)c_nm0 | ((uint64_t)c_nm1 << 32), kp.k);
+        if (u < n_units) ok = ~(uint32_t)sp_bad_from_words64((uint64_t)c_nm0 | ((uint64_t)c_nm1 << 32), kp.k);
+        const bool fast = __all(ok == 0xffffffffu);      // wave-uniform (a thread without a unit has ok = 0)
+        auto record = [&](uint32_t V, uint32_t W, uint32_t &b) {
+            const uint32_t sl = sp_slot_of32_t<ODD>(V >> sh, ~W & kp.kmask, kp);
+            b = sl >> shift1;
+            uint32_t r = (b << 24) | (sl & mask1);
+            asm volatile("" : "+v"(r));      // (formed HERE: left alone the compiler keeps slot and bucket of all 32 keys to the end of the scan)
+            return r;
+        };
+        if (fast) {
             auto f = [&](int j, uint32_t V, uint32_t W) {
-                slot[j] = kp.odd ? sp_slot_of32_t<true>(V >> sh, ~W & kp.kmask, kp)
-                                 : sp_slot_of32_t<false>(V >> sh, ~W & kp.kmask, kp);
-                if ((ok >> j) & 1u) rank[j] = atomicAdd(&hist[slot[j] >> shift1], 1u);
+                uint32_t b;
+                slot[j] = record(V, W, b);
+                rank[j] = atomicAdd(&hist[b], 1u);
+                // (without the masks the scan is one basic block, and the scheduler would form all 32 windows first: 169 registers
+                // and one block per CU; four keys at a time stay within 128)
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
             };
             sp_win_loop<0, 1, decltype(f)>::run(x, f);
+        } else if (u < n_units) {
+            auto f = [&](int j, uint32_t V, uint32_t W) {
+                uint32_t b;
+                slot[j] = record(V, W, b);
+                if ((ok >> j) & 1u) rank[j] = atomicAdd(&hist[b], 1u);
+                if ((j & 3) == 3) __builtin_amdgcn_sched_barrier(0);
+            };
+            sp_win_loop<0, 1, decltype(f)>::run(x, f);
+        } else {                 // (a thread without a unit: its records index start[] below, unconditionally -- advisor r05)
+#pragma unroll
+            for (int j = 0; j < 32; j++) slot[j] = 0;
         }
         bar();
         unsigned long long at = 0, r_lo = 0, r_hi = 0;
@@ -378,7 +407,7 @@ __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, c
             // (nothing that depends on the atomic's result before the scan below: the two waves that reserve would
             // sit out its round trip in front of a barrier the whole block waits at)
         }
-        const uint32_t total = c2_scan_F<C2_P1_ASYNC != 0>(hist, start, F1, wsum);
+        const uint32_t total = c2_scan_F<C2_P1_ASYNC != 0, C2_P1_THREADS>(hist, start, F1, wsum);
         if (threadIdx.x < F1) {
             const unsigned long long g = r_lo + at;
             // estimate mode: a run that does not fit its bucket's region is dropped (c2_tiles sees the cursor and
@@ -388,15 +417,27 @@ __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, c
             for (uint32_t i = c; i < ((c + 3u) & ~3u); i++) keys[start[threadIdx.x] + i] = ((uint32_t)threadIdx.x << 24) | C2_INVALID1;
         }
         // (the run starts of eight keys are read together: one LDS round trip per eight keys instead of one per key)
+        if (fast) {
 #pragma unroll
-        for (int j0 = 0; j0 < 32; j0 += 8) {
-            uint32_t st[8];
+            for (int j0 = 0; j0 < 32; j0 += 8) {
+                uint32_t st[8];
 #pragma unroll
-            for (int jj = 0; jj < 8; jj++) st[jj] = start[slot[j0 + jj] >> shift1];
+                for (int jj = 0; jj < 8; jj++) st[jj] = start[slot[j0 + jj] >> 24];
 #pragma unroll
-            for (int jj = 0; jj < 8; jj++) {
-                const int j = j0 + jj;
-                if ((ok >> j) & 1u) keys[st[jj] + rank[j]] = ((slot[j] >> shift1) << 24) | (slot[j] & mask1);
+                for (int jj = 0; jj < 8; jj++) keys[st[jj] + rank[j0 + jj]] = slot[j0 + jj];
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        } else {
+#pragma unroll
+            for (int j0 = 0; j0 < 32; j0 += 8) {
+                uint32_t st[8];
+#pragma unroll
+                for (int jj = 0; jj < 8; jj++) st[jj] = start[slot[j0 + jj] >> 24];
+#pragma unroll
+                for (int jj = 0; jj < 8; jj++) {
+                    const int j = j0 + jj;
+                    if ((ok >> j) & 1u) keys[st[jj] + rank[j]] = slot[j];
+                }
             }
         }
         bar();
@@ -429,6 +470,9 @@ __device__ __forceinline__ void c2_part1_body(const uint32_t *__restrict__ pk, c
         }
         bar();
     }
+    };
+    if (kp.odd) tiles(sp_odd_tag{});
+    else tiles(sp_even_tag{});
 }
 
 // ---------------------------------------------------------------- c2_part2
@@ -739,10 +783,14 @@ __global__ void __launch_bounds__(C2_C16_THREADS)
 c2_count16(const uint16_t *__restrict__ buf2, const ulonglong2 *__restrict__ span, int64_t n_fine, uint32_t lower,
            uint8_t *__restrict__ tab, unsigned long long *__restrict__ out3, uint2 *__restrict__ ovf_tmp, unsigned long long ovf_cap,
            uint32_t *__restrict__ seg_base, uint32_t *__restrict__ seg_cnt) {
-    __shared__ __attribute__((aligned(16))) uint32_t cnt[C2_FINE / 2];      // two 16-bit counters per word (a wrapped bucket: 2^14 32-bit counters)
+    // two 16-bit counters per word (a wrapped bucket: 2^14 32-bit counters) + the word the pad records of a small bucket count
+    // in (never read, never cleared)
+    __shared__ __attribute__((aligned(16))) uint32_t cnt[C2_FINE / 2 + 4];
     __shared__ unsigned long long red[16];
     __shared__ uint32_t s_nov, s_over;
     unsigned long long s = 0, n = 0;
+    const bool swar = lower <= SP_SWAR_MAX_LOWER;      // (kernel-uniform) the write-out takes both halves of a word at once
+    const uint32_t lower2 = sp_swar_rep16(lower);
     uint2 pf[C2_C16_PF];
     unsigned long long pf_lo = 0, pf_hi = 0;
     auto prefetch = [&](int64_t fbn) {
@@ -751,11 +799,12 @@ c2_count16(const uint16_t *__restrict__ buf2, const ulonglong2 *__restrict__ spa
         pf_lo = d.x;                             // (a multiple of 4 records, like the size: whole quads)
         pf_hi = d.y;
         const unsigned long long n4 = (pf_hi - pf_lo) >> 2;
+        const uint32_t n4c = n4 < 0xffffffffULL ? (uint32_t)n4 : 0xffffffffu;   // (the indices below are < 2^13)
         const uint2 *p2 = reinterpret_cast<const uint2 *>(buf2 + pf_lo);
 #pragma unroll
         for (int q = 0; q < C2_C16_PF; q++) {
-            const unsigned long long i = threadIdx.x + (unsigned long long)q * C2_C16_THREADS;
-            if (i < n4) pf[q] = p2[i];
+            const uint32_t i = threadIdx.x + (uint32_t)q * C2_C16_THREADS;
+            if (i < n4c) pf[q] = p2[i];
         }
     };
     {
@@ -772,33 +821,36 @@ c2_count16(const uint16_t *__restrict__ buf2, const ulonglong2 *__restrict__ spa
         if (threadIdx.x == 0) s_nov = s_over = 0;
         const unsigned long long lo = pf_lo, hi = pf_hi;
         const bool big = hi - lo >= 65536ULL;    // block-uniform: a counter of this bucket CAN pass 16 bits
+        const bool wide = (hi - lo) >> 32 != 0ULL;   // block-uniform: positions inside the bucket need 64 bits (no bucket of a real genome)
         const unsigned long long n4 = (hi - lo) >> 2;
         const uint2 *p2 = reinterpret_cast<const uint2 *>(buf2 + lo);
         // the bucket's records: the prefetched ones, then the rest (an average bucket holds 2.5 x what the prefetch covers) in rounds
         // of C2_C16_PF loads per lane: one load per round trip -- what this loop was -- kept 8 KB in flight per CU, i.e. ~1.4 TB/s
         // for the whole chip at 1.5 us per trip, and that, not the LDS, was the kernel's rate (round 5)
-        auto all_records = [&](auto add) {
+        // (nq: the bucket's quads in the index type -- 32 bits unless the bucket is `wide`: a bucket of the wheat-like genome holds
+        // 41 K records, and the 64-bit positions were 150 add and 110 compare instructions of this kernel)
+        auto all_records = [&](auto nq, auto add) {
+            using I = decltype(nq);
 #pragma unroll
             for (int q = 0; q < C2_C16_PF; q++) {
-                if (threadIdx.x + (unsigned long long)q * C2_C16_THREADS < n4) {
+                if ((I)(threadIdx.x + (uint32_t)q * C2_C16_THREADS) < nq) {
                     add(pf[q].x & 0xffffu);
                     add(pf[q].x >> 16);
                     add(pf[q].y & 0xffffu);
                     add(pf[q].y >> 16);
                 }
             }
-            for (unsigned long long base = (unsigned long long)C2_C16_PF * C2_C16_THREADS; base < n4;
-                 base += (unsigned long long)C2_C16_PF * C2_C16_THREADS) {
+            for (I base = (I)C2_C16_PF * C2_C16_THREADS; base < nq; base += (I)C2_C16_PF * C2_C16_THREADS) {   // (nq < 2^30 where I has 32 bits)
                 uint2 v[C2_C16_PF];
 #pragma unroll
                 for (int q = 0; q < C2_C16_PF; q++) {
                     // (unconditional, from a clamped index: a load under a condition is followed by a wait of its own)
-                    const unsigned long long i = base + threadIdx.x + (unsigned long long)q * C2_C16_THREADS;
-                    v[q] = p2[i < n4 ? i : n4 - 1ULL];
+                    const I i = base + threadIdx.x + (I)q * C2_C16_THREADS;
+                    v[q] = p2[i < nq ? i : nq - (I)1];
                 }
 #pragma unroll
                 for (int q = 0; q < C2_C16_PF; q++) {
-                    if (base + threadIdx.x + (unsigned long long)q * C2_C16_THREADS < n4) {
+                    if (base + threadIdx.x + (I)q * C2_C16_THREADS < nq) {
                         add(v[q].x & 0xffffu);
                         add(v[q].x >> 16);
                         add(v[q].y & 0xffffu);
@@ -807,16 +859,22 @@ c2_count16(const uint16_t *__restrict__ buf2, const ulonglong2 *__restrict__ spa
                 }
             }
         };
-        // a record adds 1 to its half of the word; a pad record (0xFFFF) adds 0 to the last word
         if (!big) {
-            all_records([&](uint32_t r) { atomicAdd(&cnt[(r & (C2_FINE - 1)) >> 1], ((r >> C2_B3) ^ 1u) << (16u * (r & 1u))); });
+            // a record adds 1 to its half of the word; a pad record (0xFFFF) does the same to the spare word behind the counters
+            all_records((uint32_t)n4, [&](uint32_t r) {
+                const uint32_t w = r >> 1;
+                atomicAdd(&cnt[w < (uint32_t)(C2_FINE / 2) ? w : (uint32_t)(C2_FINE / 2)], (r & 1u) ? 0x10000u : 1u);
+            });
         } else {
+            // (here a pad record adds 0 to the last word: the spare word would wrap, and a wrap is what this path looks for)
             uint32_t wrapped = 0;
-            all_records([&](uint32_t r) {
+            auto add = [&](uint32_t r) {
                 const uint32_t sh = 16u * (r & 1u), inc = ((r >> C2_B3) ^ 1u) << sh;
                 const uint32_t old = atomicAdd(&cnt[(r & (C2_FINE - 1)) >> 1], inc);
                 wrapped |= (inc != 0u && ((old >> sh) & 0xffffu) == 0xffffu) ? 1u : 0u;
-            });
+            };
+            if (!wide) all_records((uint32_t)n4, add);
+            else all_records(n4, add);
             if (wrapped) s_over = 1u;
         }
         prefetch(fb + gridDim.x);   // in flight across the write-out below
@@ -872,22 +930,55 @@ c2_count16(const uint16_t *__restrict__ buf2, const ulonglong2 *__restrict__ spa
         // floor(first record / 255) -- a slot that overflows accounts for >= 255 records, so the segment holds them whatever the
         // bucket's size; ovf_place ranks a segment by slot afterwards, the order of arrival does not matter)
         uint2 *t64 = reinterpret_cast<uint2 *>(tab + fb * C2_FINE);
-        for (int i = threadIdx.x; i < C2_FINE / 8; i += C2_C16_THREADS) {
-            const uint4 v = c4[i];
-            c4[i] = make_uint4(0, 0, 0, 0);
-            const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
-            uint32_t packed[2] = {0, 0};
+        if (swar) {
+            // both counters of a word at once (sp_swar.h): flags for `>= lower`, their number and their sum into 32-bit tallies
+            // (64 counters of at most 65535 per thread and bucket), the table bytes by a packed min and a byte permute; the
+            // overflow pairs -- 0.7 % of the slots reach `lower` on the wheat-like genome and far fewer 255 -- are the rare
+            // branch, taken per group of eight slots.  Per-slot this loop was over half of the kernel's instructions.
+            uint32_t s32 = 0, n32 = 0;
+#pragma unroll 2
+            for (int i = threadIdx.x; i < C2_FINE / 8; i += C2_C16_THREADS) {
+                const uint4 v = c4[i];
+                c4[i] = make_uint4(0, 0, 0, 0);
+                const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+                if (sp_swar_any_ge255(v.x, v.y, v.z, v.w)) {
 #pragma unroll
-            for (int j = 0; j < 8; j++) {
-                const uint32_t c = (w4[j >> 1] >> (16 * (j & 1))) & 0xffffu;
-                if (c >= lower) { s += c; n++; }
-                if (c >= 255u) {
-                    const unsigned long long pos = seg + atomicAdd(&s_nov, 1u);
-                    if (pos < ovf_cap) ovf_tmp[pos] = make_uint2((uint32_t)(fb * C2_FINE + 8 * i + j), c);
+                    for (int j = 0; j < 8; j++) {
+                        const uint32_t c = (w4[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+                        if (c >= 255u) {
+                            const unsigned long long pos = seg + atomicAdd(&s_nov, 1u);
+                            if (pos < ovf_cap) ovf_tmp[pos] = make_uint2((uint32_t)(fb * C2_FINE + 8 * i + j), c);
+                        }
+                    }
                 }
-                packed[j >> 2] |= (c < 255u ? c : 255u) << (8 * (j & 3));
+#pragma unroll
+                for (int j = 0; j < 4; j++) {
+                    const uint32_t f = sp_swar_ge_flags(w4[j], lower2);
+                    n32 += sp_swar_flag_count(f);
+                    s32 = sp_swar_flag_sum(w4[j], f, s32);
+                }
+                t64[i] = make_uint2(sp_swar_sat_bytes(v.x, v.y), sp_swar_sat_bytes(v.z, v.w));
             }
-            t64[i] = make_uint2(packed[0], packed[1]);
+            s += s32;
+            n += n32;
+        } else {
+            for (int i = threadIdx.x; i < C2_FINE / 8; i += C2_C16_THREADS) {
+                const uint4 v = c4[i];
+                c4[i] = make_uint4(0, 0, 0, 0);
+                const uint32_t w4[4] = {v.x, v.y, v.z, v.w};
+                uint32_t packed[2] = {0, 0};
+#pragma unroll
+                for (int j = 0; j < 8; j++) {
+                    const uint32_t c = (w4[j >> 1] >> (16 * (j & 1))) & 0xffffu;
+                    if (c >= lower) { s += c; n++; }
+                    if (c >= 255u) {
+                        const unsigned long long pos = seg + atomicAdd(&s_nov, 1u);
+                        if (pos < ovf_cap) ovf_tmp[pos] = make_uint2((uint32_t)(fb * C2_FINE + 8 * i + j), c);
+                    }
+                    packed[j >> 2] |= (c < 255u ? c : 255u) << (8 * (j & 3));
+                }
+                t64[i] = make_uint2(packed[0], packed[1]);
+            }
         }
         __syncthreads();
         if (threadIdx.x == 0) {
