@@ -100,6 +100,10 @@ int sp_table_overflow(sp_ctx *ctx, int chrom, void *d_pairs, int64_t cap, int64_
  *                     reaches 255 or whose summands were saturated becomes 255 and its exact sum (looked up in
  *                     the two overflow lists, absolute slots) goes to d_out_ovf -- a NEW list of the slots of this
  *                     range only, ascending (capacity `cap` pairs; SP_ENOMEM with *n_out = the number needed).
+ *                     slot_base may be ANY non-negative slot (dist.py's ranges are 64-slot aligned, not aligned to
+ *                     the 2^15-slot buckets the list is built in): the output list is ascending whatever the
+ *                     alignment.  The input lists may cover the whole table or the range only; d_out_ovf must not
+ *                     be one of them (a chain of merges alternates between two output buffers).
  *   sp_table_lengths  sum and number of the counts >= lower_count of a slice (the chromosome's contribution of this
  *                     slot range to `lengths`, Jellyfish.py:97,449, and to the dump size).                         */
 int sp_table_merge(sp_ctx *ctx, void *d_dst_u8, const void *d_dst_ovf, int64_t n_dst_ovf, const void *d_src_u8,

@@ -113,11 +113,14 @@ __device__ __forceinline__ void ovf_scan_body(const uint32_t *__restrict__ seg_c
 // overflow case: ~9 per bucket) are ranked by brute force; a bucket with many (engine 3 stages EVERY kept slot) marks
 // its slots in a 2^15-bit LDS bitmap and ranks by prefix popcount -- O(m + 1024) instead of O(m^2).
 // SPLIT: the pairs go to separate (u64 slot, u32 count) arrays, the form the list engines work on.
+// `bias`: absolute slot of the first bucket's first slot.  The counting kernels cut the whole table into buckets (bias
+// 0); sp_table_merge cuts a slice that may start at any slot, so a bucket of its LOCAL slots can straddle an absolute
+// 2^15 boundary -- the bitmap is indexed by the offset inside the local bucket, (slot - bias) mod 2^15.
 #define OVF_BRUTE 96
 template <bool SPLIT>
 __device__ __forceinline__ void ovf_place_body(const uint2 *__restrict__ tmp, const uint32_t *__restrict__ seg_base, const uint32_t *__restrict__ seg_cnt,
           const uint32_t *__restrict__ seg_off, int64_t n_buckets, uint2 *__restrict__ out,
-          unsigned long long *__restrict__ out_keys, uint32_t *__restrict__ out_cnts) {
+          unsigned long long *__restrict__ out_keys, uint32_t *__restrict__ out_cnts, uint32_t bias) {
     __shared__ uint32_t bits[4][1 << (SP_OVF_SHIFT - 5)], pre[4][1 << (SP_OVF_SHIFT - 5)];
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int64_t b = (int64_t)blockIdx.x * 4 + w;
@@ -147,7 +150,7 @@ __device__ __forceinline__ void ovf_place_body(const uint2 *__restrict__ tmp, co
     for (int i = lane; i < NW; i += 64) bits[w][i] = 0;
     __builtin_amdgcn_wave_barrier();
     for (uint32_t j = lane; j < m; j += 64) {
-        const uint32_t r = src[j].x & ((1u << SP_OVF_SHIFT) - 1u);
+        const uint32_t r = (src[j].x - bias) & ((1u << SP_OVF_SHIFT) - 1u);
         atomicOr(&bits[w][r >> 5], 1u << (r & 31u));
     }
     __builtin_amdgcn_wave_barrier();
@@ -168,7 +171,7 @@ __device__ __forceinline__ void ovf_place_body(const uint2 *__restrict__ tmp, co
     __builtin_amdgcn_wave_barrier();
     for (uint32_t j = lane; j < m; j += 64) {
         const uint2 e = src[j];
-        const uint32_t r = e.x & ((1u << SP_OVF_SHIFT) - 1u);
+        const uint32_t r = (e.x - bias) & ((1u << SP_OVF_SHIFT) - 1u);
         put(pre[w][r >> 5] + __popc(bits[w][r >> 5] & ((1u << (r & 31u)) - 1u)), e);
     }
 }
@@ -307,8 +310,8 @@ template <bool SPLIT>
 __global__ void __launch_bounds__(256)
 ovf_place(const uint2 *__restrict__ tmp, const uint32_t *__restrict__ seg_base, const uint32_t *__restrict__ seg_cnt,
           const uint32_t *__restrict__ seg_off, int64_t n_buckets, uint2 *__restrict__ out,
-          unsigned long long *__restrict__ out_keys, uint32_t *__restrict__ out_cnts) {
-    ovf_place_body<SPLIT>(tmp, seg_base, seg_cnt, seg_off, n_buckets, out, out_keys, out_cnts);
+          unsigned long long *__restrict__ out_keys, uint32_t *__restrict__ out_cnts, uint32_t bias) {
+    ovf_place_body<SPLIT>(tmp, seg_base, seg_cnt, seg_off, n_buckets, out, out_keys, out_cnts, bias);
 }
 // one chromosome per blockIdx.y (sp_c2batch.h)
 __global__ void __launch_bounds__(1024)
@@ -319,7 +322,7 @@ ovf_scan_b(const c2_bdesc *__restrict__ desc, int64_t n) {
 __global__ void __launch_bounds__(256)
 ovf_place_list_b(const c2_bdesc *__restrict__ desc, int64_t n_buckets) {
     const c2_bdesc D = desc[blockIdx.y];
-    ovf_place_body<true>(D.stage, D.seg_base, D.seg_cnt, D.seg_off, n_buckets, (uint2 *)nullptr, D.out_keys, D.out_cnts);
+    ovf_place_body<true>(D.stage, D.seg_base, D.seg_cnt, D.seg_off, n_buckets, (uint2 *)nullptr, D.out_keys, D.out_cnts, 0u);
 }
 int sp_ovf_finalize_split_batch(sp_ctx *ctx, const c2_bdesc *d_desc, int n_chrom, int64_t n_buckets) {
     SP_LAUNCH(ctx, "ovf_scan", ovf_scan_b, dim3(1, (unsigned)n_chrom), dim3(1024), 0, d_desc, n_buckets);
@@ -349,11 +352,12 @@ kx_lengths(sp_tabref T, int64_t slot_base, int64_t n, uint32_t lower, unsigned l
 }
 
 // Lay the overflow segments a counting kernel left behind out in bucket order (= ascending slot order).
+// slot_base: first slot of bucket 0 (0 for a whole table; the slice's base for sp_table_merge, any alignment).
 static int ovf_finalize_to(sp_ctx *ctx, uint2 *out, const uint2 *tmp, const uint32_t *seg_base, const uint32_t *seg_cnt,
-                           uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total = nullptr) {
+                           uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total = nullptr, int64_t slot_base = 0) {
     SP_LAUNCH(ctx, "ovf_scan", ovf_scan, dim3(1), dim3(1024), 0, seg_cnt, n_buckets, seg_off, d_total);
     SP_LAUNCH(ctx, "ovf_place", ovf_place<false>, dim3((unsigned)((n_buckets + 3) / 4)), dim3(256), 0, tmp, seg_base, seg_cnt,
-              (const uint32_t *)seg_off, n_buckets, out, (unsigned long long *)nullptr, (uint32_t *)nullptr);
+              (const uint32_t *)seg_off, n_buckets, out, (unsigned long long *)nullptr, (uint32_t *)nullptr, (uint32_t)slot_base);
     return SP_OK;
 }
 int sp_ovf_finalize(sp_ctx *ctx, sp_chrom &c, const uint2 *tmp, const uint32_t *seg_base, const uint32_t *seg_cnt,
@@ -376,7 +380,7 @@ int sp_ovf_finalize_split(sp_ctx *ctx, unsigned long long *keys, uint32_t *cnts,
                           const uint32_t *seg_cnt, uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total) {
     SP_LAUNCH(ctx, "ovf_scan", ovf_scan, dim3(1), dim3(1024), 0, seg_cnt, n_buckets, seg_off, d_total);
     SP_LAUNCH(ctx, "ovf_place_list", ovf_place<true>, dim3((unsigned)((n_buckets + 3) / 4)), dim3(256), 0, tmp, seg_base,
-              seg_cnt, (const uint32_t *)seg_off, n_buckets, (uint2 *)nullptr, keys, cnts);
+              seg_cnt, (const uint32_t *)seg_off, n_buckets, (uint2 *)nullptr, keys, cnts, 0u);
     return SP_OK;
 }
 
@@ -832,7 +836,7 @@ int sp_table_merge(sp_ctx *ctx, void *d_dst_u8, const void *d_dst_ovf, int64_t n
     if ((int64_t)h > cap)
         return sp_fail(ctx, SP_ENOMEM, "sp_table_merge: %lld overflow pairs exceed the capacity %lld (the tables are now "
                        "inconsistent: merge again from fresh inputs)", (long long)h, (long long)cap);
-    if (h) return ovf_finalize_to(ctx, (uint2 *)d_out_ovf, tmp, seg_base, seg_cnt, seg_off, n_buckets);
+    if (h) return ovf_finalize_to(ctx, (uint2 *)d_out_ovf, tmp, seg_base, seg_cnt, seg_off, n_buckets, nullptr, slot_base);
     return SP_OK;
 }
 
