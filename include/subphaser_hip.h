@@ -238,6 +238,18 @@ int sp_stack_enrich(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, int64_t w
 int sp_kmer_ttest(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
                   const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                   double *pvals, double *means);
+/* The same test for groups of 1 .. 65536 chromosomes (scaffold-level assemblies; SP_EUNSUP beyond, SP_ENOMEM with the
+ * size when the workspace does not fit), same arguments, `counts` host or device.  Two definitions are the reference's
+ * to the bit, for lists of any length:
+ *   means[row][g]  np.mean of the group's list in list order (Cluster.py:181): numpy's pairwise sum / n;
+ *   top, second    by the order key -sum(x) / len(x) (Cluster.py:183): the sum added strictly left to right,
+ *                  ties in group order.  (sp_kmer_ttest orders by the pairwise mean; the two agree except where two
+ *                  groups' keys meet in the last bits.)
+ * The variances are numpy's (pairwise sums of squared deviations from the pairwise mean); the p-value's incomplete beta
+ * keeps a relative 1e-10 up to df = 131070, where the prefactor sp_kmer_ttest uses does not.                     */
+int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
+                       const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
+                       double *pvals, double *means);
 
 /* ---- multi-GPU, k > 15 ----------------------------------------------------------------------
  * Twin of sp_tables_bind / sp_filter_view for 64-bit keys ("for k > 16 the exchange

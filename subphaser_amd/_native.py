@@ -23,7 +23,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -111,6 +111,7 @@ def load():
     L.sp_enrich.argtypes = [vp, vp, i64, ci, dbl, dbl, vp, vp, vp, vp]
     L.sp_enrich_dev.argtypes = [vp, vp, i64, ci, dbl, dbl, vp, vp, vp, vp]
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -754,6 +755,15 @@ class Context:
         filter_fetch returns them), lengths: int64 [C], groups: list of chromosome-index lists in sorted
         subgenome-name order.  Returns (top, second, pvals, means [M, n_groups]).
         counts may also be (device pointer, M, C): rows staged on the device earlier (stage_rows)."""
+        return self._kmer_ttest(self.L.sp_kmer_ttest, counts, lengths, groups)
+
+    def kmer_ttest_wide(self, counts, lengths, groups):
+        """kmer_ttest for subgenomes of up to 65536 chromosomes (sp_kmer_ttest_wide): same arguments and results.
+        means are np.mean of a group's list (pairwise), top / second follow the reference's order key, the
+        left-to-right sum over the list divided by its length (Cluster.py:181-183)."""
+        return self._kmer_ttest(self.L.sp_kmer_ttest_wide, counts, lengths, groups)
+
+    def _kmer_ttest(self, entry, counts, lengths, groups):
         if isinstance(counts, tuple):
             d_ptr, M, Cn = counts
             cptr = C.c_void_p(int(d_ptr))
@@ -767,8 +777,8 @@ class Context:
         gch = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups]), np.int32)
         top, second = np.empty(M, np.int32), np.empty(M, np.int32)
         pvals, means = np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
-        self._ck(self.L.sp_kmer_ttest(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
-                                      _p(top), _p(second), _p(pvals), _p(means)))
+        self._ck(entry(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
+                       _p(top), _p(second), _p(pvals), _p(means)))
         return top, second, pvals, means
 
     def stage_rows(self, counts):

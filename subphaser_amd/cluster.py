@@ -132,43 +132,39 @@ class Cluster:
         (the CLI runs it on a writer thread while the mapping stage uses the labels)."""
         if test_method not in TEST_METHODS:
             raise ValueError("test_method must be one of {}".format(TEST_METHODS))
-        from scipy import special
         sgs = sorted(set(self.d_sg.values()))
         groups = [[i for i, c in enumerate(self.chrs) if self.d_sg[c] == sg] for sg in sgs]
         X = self.raw_data
         M = X.shape[0]
         ctx = getattr(self, "_ctx", None)
-        # the kernel keeps a group's values in registers: at most TTEST_MAX_GROUP chromosomes per subgenome
-        # (sp_kmer_ttest returns SP_EUNSUP beyond); scaffold-level runs with larger groups take the numpy code below
-        if (test_method == "ttest_ind" and M and ctx is not None and hasattr(ctx, "kmer_ttest")
-                and getattr(self, "_counts", None) is not None and self._lengths is not None
-                and max(len(g) for g in groups) <= TTEST_MAX_GROUP):
-            # device path: one thread per k-mer (csrc/sp_enrich.hip k7_ttest); the numpy code below is the same test
-            # for matrices that only exist as a `.kmer.mat` file or behind a context without the kernel
-            staged = getattr(self, "_counts_dev", None)      # rows already on the device (the CLI stages them early)
+        # k7_ttest keeps a group's values in registers: at most TTEST_MAX_GROUP chromosomes per subgenome (sp_kmer_ttest
+        # returns SP_EUNSUP beyond).  Scaffold-level runs with larger groups, up to TTEST_WIDE_MAX_GROUP, take
+        # k7_ttest_wide* (sp_kmer_ttest_wide) when the context has it, the numpy code below otherwise.
+        biggest = max(len(g) for g in groups)
+        entry = None
+        if (test_method == "ttest_ind" and M and ctx is not None
+                and getattr(self, "_counts", None) is not None and self._lengths is not None):
+            if biggest <= TTEST_MAX_GROUP:
+                entry = getattr(ctx, "kmer_ttest", None)
+            elif biggest <= TTEST_WIDE_MAX_GROUP:
+                entry = getattr(ctx, "kmer_ttest_wide", None)
+        staged = getattr(self, "_counts_dev", None)      # rows already on the device (the CLI stages them early)
+        if entry is not None:
+            # device path: a thread per k-mer (csrc/sp_enrich.hip); the numpy code below is the same test for matrices
+            # that only exist as a `.kmer.mat` file or behind a context without the kernel
             try:
-                top, second, pvals, means = ctx.kmer_ttest(staged if staged else self._counts, self._lengths, groups)
+                top, second, pvals, means = entry(staged if staged else self._counts, self._lengths, groups)
             finally:
-                if staged and hasattr(ctx, "release_rows"):     # M x C x 4 bytes of HBM nobody reads again
-                    ctx.release_rows()
-                    self._counts_dev = None
+                self._release_staged(ctx, staged)       # M x C x 4 bytes of HBM nobody reads again
             return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
-        means = np.stack([X[:, g].mean(axis=1) for g in groups], axis=1) if M else np.zeros((0, len(sgs)))
-        # the reference orders groups by -sum/len (Cluster.py:182); ties keep SG-name order (stable)
-        keyv = np.stack([-(X[:, g].sum(axis=1) / len(g)) for g in groups], axis=1) if M else means
-        order = np.argsort(keyv, axis=1, kind="stable")
-        top, second = order[:, 0], (order[:, 1] if len(sgs) > 1 else order[:, 0])
-        pvals = np.ones(M)
-        for a in range(len(sgs)):
-            for b in range(len(sgs)):
-                if a == b:
-                    continue
-                sel = np.flatnonzero((top == a) & (second == b))
-                if sel.size and test_method == "ttest_ind":
-                    pvals[sel] = _ttest_ind(X[np.ix_(sel, groups[a])], X[np.ix_(sel, groups[b])], special)
-                elif sel.size:      # the other scipy tests the reference accepts (Cluster.py:178-194), row by row
-                    pvals[sel] = _scipy_rows(test_method, X[np.ix_(sel, groups[a])], X[np.ix_(sel, groups[b])])
+        self._release_staged(ctx, staged)               # the numpy code reads the host matrix
+        top, second, pvals, means = numpy_kmer_test(X, groups, test_method)
         return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
+
+    def _release_staged(self, ctx, staged):
+        if staged and hasattr(ctx, "release_rows"):
+            ctx.release_rows()
+            self._counts_dev = None
 
     def _write_kmers(self, fout, sgs, top, pvals, means, max_pval, defer=False):
         with np.errstate(invalid="ignore"):
@@ -196,6 +192,30 @@ class Cluster:
 
 TEST_METHODS = ("ttest_ind", "kruskal", "wilcoxon", "mannwhitneyu")
 TTEST_MAX_GROUP = 64     # SP_TT_MAXG in csrc/sp_enrich.hip
+TTEST_WIDE_MAX_GROUP = 65536     # SP_TT_WIDE_MAX in csrc/sp_ttest.h
+
+
+def numpy_kmer_test(X, groups, test_method="ttest_ind"):
+    """Cluster.output_kmers' test in numpy on the M x C fp64 matrix (matrices without a context, the other
+    `-test_method`s): (top, second, pvals, means [M, n_groups])."""
+    from scipy import special
+    M, G = X.shape[0], len(groups)
+    means = np.stack([X[:, g].mean(axis=1) for g in groups], axis=1) if M else np.zeros((0, G))
+    # the reference orders groups by -sum/len (Cluster.py:182); ties keep SG-name order (stable)
+    keyv = np.stack([-(X[:, g].sum(axis=1) / len(g)) for g in groups], axis=1) if M else means
+    order = np.argsort(keyv, axis=1, kind="stable")
+    top, second = order[:, 0], (order[:, 1] if G > 1 else order[:, 0])
+    pvals = np.ones(M)
+    for a in range(G):
+        for b in range(G):
+            if a == b:
+                continue
+            sel = np.flatnonzero((top == a) & (second == b))
+            if sel.size and test_method == "ttest_ind":
+                pvals[sel] = _ttest_ind(X[np.ix_(sel, groups[a])], X[np.ix_(sel, groups[b])], special)
+            elif sel.size:      # the other scipy tests the reference accepts (Cluster.py:178-194), row by row
+                pvals[sel] = _scipy_rows(test_method, X[np.ix_(sel, groups[a])], X[np.ix_(sel, groups[b])])
+    return top, second, pvals, means
 
 
 def _kruskal_rows(a, b):

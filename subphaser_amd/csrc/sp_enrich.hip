@@ -8,6 +8,7 @@
 // margins of 2e8 where a difference of lgamma() values loses 6-7 digits; the
 // tail is then summed by the exact term recurrence.  All arithmetic is fp64.
 #include "sp_device.h"
+#include "sp_ttest.h"
 
 #define SP_MAX_INT_CLAMP (2147483647LL / 10)  // Stats.py:9
 #define SP_ENRICH_MAXS 32
@@ -329,6 +330,228 @@ extern "C" int sp_kmer_ttest(sp_ctx *ctx, const uint32_t *counts, int64_t M, int
     SP_LAUNCH(ctx, "k7_ttest", k7_ttest, dim3((unsigned)((M + 127) / 128)), dim3(128), 0, d_counts,
               (long long)M, C, (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, d_top, d_sec, d_p,
               d_means);
+    SP_HIP(ctx, hipMemcpyAsync(top, d_top, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(second, d_sec, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(pvals, d_p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(means, d_means, (size_t)M * n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
+    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    return SP_OK;
+}
+
+// ----------------------------------------------------------------- f-1, subgenomes of more than SP_TT_MAXG chromosomes
+// The same test for groups of up to SP_TT_WIDE_MAX chromosomes (scaffold-level assemblies: every scaffold is assigned to
+// a subgenome).  No array sized by the group: a thread still owns a row and adds its values in list order, but the
+// values stream through the accumulator of sp_ttest.h (numpy's pairwise sum, bit for bit, from a per-group program
+// built on the host) and the counts reach the thread through an LDS transpose, so that global reads run along the rows:
+//   a workgroup = one wave = SP_TW_ROWS rows; per chunk of SP_TW_COLS entries of a group's column list, lane l loads
+//   column entry l of every row (one row segment per load instruction), stores it at [row][l] with an odd pitch, and
+//   after the barrier reads [its row][0 .. SP_TW_COLS) -- conflict-free both ways.  The column lengths of the chunk sit
+//   beside the tile and are read as broadcasts.  Control flow depends on the group sizes only: uniform across lanes.
+// k7_ttest_wide_means (pass 1): means[r][g] = np.mean of the list (pairwise); top / second by the reference's own order
+//   key -sum(x) / len(x), the Python sum added strictly left to right (Cluster.py:183) -- the two differ in the last bits.
+// k7_ttest_wide_test (pass 2): sweeps every group again with (v - mean)^2 and keeps the variances of top and second (G is
+//   2..8 in practice and every column belongs to one group: one more read of the matrix, no divergence), then t and p as
+//   k7_ttest forms them, the p-value from sp_tt_pvalue (accurate at df in the thousands, where d_betainc is not).
+#define SP_TW_ROWS 64
+#define SP_TW_COLS 64
+#define SP_TW_PITCH (SP_TW_COLS + 1)
+struct sp_tw_lds {
+    uint32_t tile[SP_TW_ROWS * SP_TW_PITCH];
+    double len[SP_TW_COLS];
+    uint32_t prog[SP_TW_COLS / 8];              // the chunk's program bytes
+    double stack[SP_TT_DEPTH * SP_TW_ROWS];     // [depth][lane]
+};
+struct sp_tw_stack {
+    double *base;                               // &stack[lane]
+    __device__ __forceinline__ double &at(int d) { return base[d * SP_TW_ROWS]; }
+};
+// one group of one row tile: returns P(f(v)) over the group's list, f(v) = v (SQ = false; *key gets the left-to-right sum)
+// or (v - mean)^2 (SQ = true)
+template <bool SQ>
+__device__ __forceinline__ double
+tw_group(sp_tw_lds &L, const uint32_t *__restrict__ counts, long long r0, long long M, int C, const double *__restrict__ chrom_len,
+         const int *__restrict__ gch /* the group's list */, int n, const uint8_t *__restrict__ prog /* the group's program */,
+         double mean, double *key) {
+    const int lane = threadIdx.x;
+    sp_tt_acc acc;
+    sp_tw_stack st{L.stack + lane};
+    sp_tt_begin(acc);
+    double seq = 0.0;
+    const int nfull = n - n % 8;
+    for (int c0 = 0; c0 < n; c0 += SP_TW_COLS) {
+        const int valid = n - c0 < SP_TW_COLS ? n - c0 : SP_TW_COLS;
+        __syncthreads();                        // the chunk before has been consumed
+        int col = 0;
+        if (lane < valid) {
+            col = gch[c0 + lane];
+            L.len[lane] = chrom_len[col];
+        }
+        if (lane < SP_TW_COLS / 8 && c0 + lane * 8 + 8 <= nfull) L.prog[lane] = prog[(c0 >> 3) + lane];
+        // every address is in bounds whatever the lane: rows past the last repeat it, lanes past the chunk read column
+        // 0 (nobody consumes either), so the loads carry no branch and sixteen of them are in flight per lane
+        const uint32_t *src = counts + col;
+#pragma unroll 1
+        for (int rb = 0; rb < SP_TW_ROWS; rb += 16) {
+            uint32_t c[16];
+#pragma unroll
+            for (int j = 0; j < 16; j++) {
+                const long long row = r0 + rb + j < M ? r0 + rb + j : M - 1;
+                c[j] = src[row * C];
+            }
+#pragma unroll
+            for (int j = 0; j < 16; j++) L.tile[(rb + j) * SP_TW_PITCH + lane] = c[j];
+        }
+        __syncthreads();
+        const uint32_t *mine = L.tile + lane * SP_TW_PITCH;
+        const int full_here = (nfull - c0 < valid ? nfull - c0 : valid);      // values of this chunk that lie in whole blocks
+        for (int i = 0; i < full_here; i += 8) {
+            double v[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                v[j] = (double)mine[i + j] / L.len[i + j];
+                if (SQ) { const double d = v[j] - mean; v[j] = d * d; }
+                else seq += v[j];
+            }
+            sp_tt_block(acc, v, (unsigned)__builtin_amdgcn_readfirstlane((int)L.prog[i >> 3]), st);
+        }
+        for (int i = full_here > 0 ? full_here : 0; i < valid; i++) {        // the n % 8 tail, in the last chunk only
+            double v = (double)mine[i] / L.len[i];
+            if (SQ) { const double d = v - mean; v = d * d; }
+            else seq += v;
+            sp_tt_tail(acc, v);
+        }
+    }
+    if (!SQ) *key = seq;
+    return sp_tt_finish(acc, st);
+}
+
+__global__ void __launch_bounds__(SP_TW_ROWS)
+k7_ttest_wide_means(const uint32_t *__restrict__ counts, long long M, int C, const double *__restrict__ chrom_len, int G,
+                    const int *__restrict__ goff, const int *__restrict__ gchrom, const int *__restrict__ poff,
+                    const uint8_t *__restrict__ prog, int *__restrict__ top, int *__restrict__ second,
+                    double *__restrict__ means) {
+    __shared__ sp_tw_lds L;
+    const long long r0 = (long long)blockIdx.x * SP_TW_ROWS, r = r0 + threadIdx.x;
+    int t1 = -1, t2 = -1;
+    double k1 = 0, k2 = 0;
+    for (int g = 0; g < G; g++) {
+        const int n = goff[g + 1] - goff[g];
+        double seq;
+        const double mean = tw_group<false>(L, counts, r0, M, C, chrom_len, gchrom + goff[g], n, prog + poff[g], 0.0, &seq) / (double)n;
+        const double key = seq / (double)n;
+        if (r < M) means[r * G + g] = mean;
+        if (t1 < 0 || key > k1) { t2 = t1; k2 = k1; t1 = g; k1 = key; }
+        else if (t2 < 0 || key > k2) { t2 = g; k2 = key; }
+    }
+    if (t2 < 0) t2 = t1;
+    if (r < M) {
+        top[r] = t1;
+        second[r] = t2;
+    }
+}
+
+__global__ void __launch_bounds__(SP_TW_ROWS)
+k7_ttest_wide_test(const uint32_t *__restrict__ counts, long long M, int C, const double *__restrict__ chrom_len, int G,
+                   const int *__restrict__ goff, const int *__restrict__ gchrom, const int *__restrict__ poff,
+                   const uint8_t *__restrict__ prog, const int *__restrict__ top, const int *__restrict__ second,
+                   const double *__restrict__ means, double *__restrict__ pvals) {
+    __shared__ sp_tw_lds L;
+    const long long r0 = (long long)blockIdx.x * SP_TW_ROWS, r = r0 + threadIdx.x;
+    const long long rc = r < M ? r : M - 1;     // lanes past the last row go through the motions on it and store nothing
+    const int t1 = top[rc], t2 = second[rc];
+    double var1 = 0, var2 = 0, mu1 = 0, mu2 = 0;
+    int n1 = 1, n2 = 1;
+    for (int g = 0; g < G; g++) {
+        const int n = goff[g + 1] - goff[g];
+        const double mean = means[rc * G + g];
+        const double ss = tw_group<true>(L, counts, r0, M, C, chrom_len, gchrom + goff[g], n, prog + poff[g], mean, nullptr);
+        const double var = n > 1 ? ss / (double)(n - 1) : 0.0;
+        if (g == t1) { var1 = var; mu1 = mean; n1 = n; }
+        if (g == t2) { var2 = var; mu2 = mean; n2 = n; }
+    }
+    const double df = (double)(n1 + n2) - 2.0;
+    double p;
+    if (!(df > 0.0)) {
+        p = __longlong_as_double(0x7ff8000000000000LL);
+    } else {
+        const double svar = ((n1 - 1) * var1 + (n2 - 1) * var2) / df;
+        const double denom = sqrt(svar * (1.0 / n1 + 1.0 / n2));
+        const double t = (mu1 - mu2) / denom;
+        if (t != t) p = t;
+        else if (isinf(t)) p = 0.0;
+        else p = sp_tt_pvalue(df, t);
+    }
+    if (r < M) pvals[r] = p;
+}
+
+extern "C" int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
+                                  const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
+                                  double *pvals, double *means) {
+    if (!ctx || M < 0 || C < 1 || n_groups < 1 || !lengths || !group_off || !group_chrom ||
+        (M > 0 && (!counts || !top || !second || !pvals || !means)))
+        return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest_wide: bad arguments");
+    std::vector<int> poff((size_t)n_groups + 1, 0);
+    for (int g = 0; g < n_groups; g++) {
+        const int n = group_off[g + 1] - group_off[g];
+        if (n < 1 || n > SP_TT_WIDE_MAX)
+            return sp_fail(ctx, SP_EUNSUP, "sp_kmer_ttest_wide: a subgenome with %d chromosomes (1..%d supported)", n, SP_TT_WIDE_MAX);
+        for (int j = group_off[g]; j < group_off[g + 1]; j++)
+            if (group_chrom[j] < 0 || group_chrom[j] >= C) return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest_wide: chromosome index out of range");
+        poff[(size_t)g + 1] = poff[(size_t)g] + n / 8;
+    }
+    if (M == 0) return SP_OK;
+    // the summation program of every group: one byte per block of 8 values (sp_ttest.h)
+    std::vector<uint8_t> hprog((size_t)poff[(size_t)n_groups] + 1, 0);
+    for (int g = 0; g < n_groups; g++) {
+        const int depth = sp_tt_program(group_off[g + 1] - group_off[g], hprog.data() + poff[(size_t)g]);
+        if (depth > SP_TT_DEPTH) return sp_fail(ctx, SP_EUNSUP, "sp_kmer_ttest_wide: summation stack of %d (%d supported)", depth, SP_TT_DEPTH);
+    }
+    SP_HIP(ctx, hipSetDevice(ctx->device));
+    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t nuc = (size_t)group_off[n_groups];
+    bool on_device = false;      // rows staged on this device earlier are read in place, as in sp_kmer_ttest
+    {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, counts) == hipSuccess)
+            on_device = at.type == hipMemoryTypeDevice && at.device == ctx->device;
+        else
+            (void)hipGetLastError();
+    }
+    const size_t rows_bytes = on_device ? 0 : al((size_t)M * C * 4);
+    const size_t need = rows_bytes + al((size_t)C * 8) + 2 * al((size_t)(n_groups + 1) * 4) + al(nuc * 4) + al(hprog.size()) +
+                        2 * al((size_t)M * 4) + al((size_t)M * 8) + al((size_t)M * n_groups * 8);
+    int rc = sp_buf_ensure(ctx, ctx->b_tt, (int64_t)need);
+    if (rc == SP_ENOMEM)
+        return sp_fail(ctx, SP_ENOMEM, "sp_kmer_ttest_wide: a workspace of %lld bytes (%lld rows x %d chromosomes%s) does not fit on the device",
+                       (long long)need, (long long)M, C, on_device ? ", rows already staged" : "");
+    if (rc) return rc;
+    char *q = (char *)ctx->b_tt.p;
+    const uint32_t *d_counts = on_device ? counts : (const uint32_t *)q; q += rows_bytes;
+    double *d_len = (double *)q; q += al((size_t)C * 8);
+    int *d_goff = (int *)q; q += al((size_t)(n_groups + 1) * 4);
+    int *d_poff = (int *)q; q += al((size_t)(n_groups + 1) * 4);
+    int *d_gch = (int *)q; q += al(nuc * 4);
+    uint8_t *d_prog = (uint8_t *)q; q += al(hprog.size());
+    int *d_top = (int *)q; q += al((size_t)M * 4);
+    int *d_sec = (int *)q; q += al((size_t)M * 4);
+    double *d_p = (double *)q; q += al((size_t)M * 8);
+    double *d_means = (double *)q;
+    std::vector<double> hl((size_t)C);
+    for (int c = 0; c < C; c++) hl[(size_t)c] = (double)lengths[c];
+    if (!on_device)
+        SP_HIP(ctx, hipMemcpyAsync((void *)d_counts, counts, (size_t)M * C * 4, hipMemcpyDefault, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_len, hl.data(), (size_t)C * 8, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_goff, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_gch, group_chrom, nuc * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_prog, hprog.data(), hprog.size(), hipMemcpyHostToDevice, ctx->stream));
+    const dim3 grid((unsigned)((M + SP_TW_ROWS - 1) / SP_TW_ROWS));
+    SP_LAUNCH(ctx, "k7_ttest_wide_means", k7_ttest_wide_means, grid, dim3(SP_TW_ROWS), 0, d_counts, (long long)M, C,
+              (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, (const int *)d_poff,
+              (const uint8_t *)d_prog, d_top, d_sec, d_means);
+    SP_LAUNCH(ctx, "k7_ttest_wide_test", k7_ttest_wide_test, grid, dim3(SP_TW_ROWS), 0, d_counts, (long long)M, C,
+              (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, (const int *)d_poff,
+              (const uint8_t *)d_prog, (const int *)d_top, (const int *)d_sec, (const double *)d_means, d_p);
     SP_HIP(ctx, hipMemcpyAsync(top, d_top, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(second, d_sec, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(pvals, d_p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
