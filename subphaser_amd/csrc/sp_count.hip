@@ -5,6 +5,7 @@
 // (reference: subphaser/Jellyfish.py:671-704).
 #include "sp_device.h"
 #include "sp_c2batch.h"
+#include "sp_internal.h"
 
 // ----------------------------------------------------------------- K1 / engine 1
 // Baseline engine: one global atomic per k-mer occurrence into the dense
@@ -243,15 +244,6 @@ static int grid_for(sp_ctx *ctx, int64_t work_items, int per_block, int max_per_
     if (b < 1) b = 1;
     return (int)b;
 }
-
-int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower,
-                     unsigned long long *d_len4, bool exact, sp_sparse_chrom *list);  // sp_count2.hip
-int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kparams &kp, int lower, unsigned long long *d_len);   // sp_count2.hip
-void sp_sparse_release(sp_ctx *ctx);                                                  // sp_sparse.hip
-bool sp_engine2_supported(int64_t nslots);
-int sp_sparse_count(sp_ctx *ctx, int k, int lower);                                   // sp_sparse.hip
-int sp_sparse_count3(sp_ctx *ctx, int k, int lower);                                  // sp_sparse2.hip
-int sp_sparse_dump(sp_ctx *ctx, int chrom, uint64_t *keys, uint32_t *counts);
 
 // ----------------------------------------------------------------- merging two byte tables (multi-GPU)
 // A chromosome whose bases were counted by two ranks arrives at the rank that filters a slot range as two

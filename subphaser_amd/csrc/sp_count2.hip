@@ -24,6 +24,7 @@
 //   0.625 x2 (scans) + 3 w + 3 r + 2 w + 2 r + 1 x slots/base (table write).
 #include "sp_device.h"
 #include "sp_c2batch.h"
+#include "sp_internal.h"
 #include "sp_swar.h"
 
 #define C2_B3 15                      // slot bits resolved inside LDS
@@ -1519,10 +1520,6 @@ c2_count_list_b(const c2_bdesc *__restrict__ desc, int64_t n_fine, uint32_t lowe
     c2_count_list_body<C2L_DEPTH, C2L_PF>(D.buf2, D.span, n_fine, lower, D.d_len4, D.stage, D.stage_cap, D.seg_base, D.seg_cnt);
 }
 
-int sp_ovf_finalize(sp_ctx *ctx, sp_chrom &c, const uint2 *tmp, const uint32_t *seg_base, const uint32_t *seg_cnt,
-                    uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total);   // sp_count.hip
-int sp_ovf_finalize_split(sp_ctx *ctx, unsigned long long *keys, uint32_t *cnts, const uint2 *tmp, const uint32_t *seg_base,
-                          const uint32_t *seg_cnt, uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total);
 
 bool sp_engine2_supported(int64_t nslots) {
     c2_plan p;
@@ -1713,7 +1710,6 @@ int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower, 
 // Same chain, same layout arithmetic as sp_count_engine2 (estimate mode only: a chromosome whose flag comes back up is
 // counted again, alone, from the exact histogram by the caller).  Workspace: the zeroed heads (histogram .. cursors) of all
 // chromosomes back to back -- one memset -- then their bodies.
-int sp_ovf_finalize_split_batch(sp_ctx *ctx, const c2_bdesc *d_desc, int n_chrom, int64_t n_buckets);   // sp_count.hip
 int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kparams &kp, int lower, unsigned long long *d_len /* 4 per chromosome */) {
     c2_plan P;
     if (!c2_make_plan(ctx->nslots, P))

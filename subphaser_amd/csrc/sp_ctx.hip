@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include "sp_common.h"
+#include "sp_internal.h"
 
 thread_local std::string g_sp_err;
 
@@ -78,7 +79,6 @@ void sp_prof_flush(sp_ctx *ctx) {
     ctx->prof_pending.clear();
 }
 
-void sp_sparse_release(sp_ctx *ctx);   // sp_sparse.hip
 
 extern "C" {
 

@@ -1,5 +1,5 @@
-// sp_filter.h -- the per-k-mer decision of the differential filter, shared by the dense (sp_filter.hip)
-// and the sparse (sp_sparse.hip) engines.
+// sp_filter.h -- the per-k-mer decision of the differential filter and the upload of its set structure, shared by
+// the dense (sp_filter.hip) and the list (sp_listfilter.hip) filters.
 #pragma once
 #include "sp_device.h"
 
@@ -14,6 +14,42 @@ struct sp_fsets {
     const double *unit_den, *unit_inv;   // per-unit denominators and their reciprocals
     double min_fold, min_freq, max_freq, ratio;
 };
+
+// The set structure in device memory: set_off | unit_off | unit_chrom (room for uc_room entries) | den (the per-unit
+// denominators, then their reciprocals), each at a 256-byte-aligned offset.  sp_fsets_bytes sizes it; sp_fsets_upload
+// copies the four arrays to `dst`, a place of that size inside a device buffer (asynchronously: the host arrays live
+// until the stream is synchronized), counts n_multi and returns the filled sp_fsets in F.
+inline size_t sp_fsets_carve(sp_carve cv, int n_sets, int n_units, size_t uc_room, sp_fsets &F) {
+    F.set_off = cv.take<int32_t>((size_t)n_sets + 1);
+    F.unit_off = cv.take<int32_t>((size_t)n_units + 1);
+    F.unit_chrom = cv.take<int32_t>(uc_room);
+    F.unit_den = cv.take<double>((size_t)n_units * 2);
+    F.unit_inv = F.unit_den + n_units;
+    return cv.off;
+}
+inline size_t sp_fsets_bytes(int n_sets, int n_units, size_t uc_room) {
+    sp_fsets F;
+    return sp_fsets_carve(sp_carve(), n_sets, n_units, uc_room, F);
+}
+inline hipError_t sp_fsets_upload(hipStream_t stream, void *dst, int n_sets, const int32_t *set_off, const int32_t *unit_off,
+                                  const int32_t *unit_chrom, size_t uc_room, const double *den, double min_fold,
+                                  int baseline, double min_freq, double max_freq, double ratio, sp_fsets &F) {
+    const int n_units = set_off[n_sets], n_uc = unit_off[n_units];
+    sp_fsets_carve(sp_carve(dst), n_sets, n_units, uc_room, F);
+    F.n_sets = n_sets;
+    F.n_multi = 0;
+    for (int st = 0; st < n_sets; st++) F.n_multi += (set_off[st + 1] - set_off[st]) > 1;
+    F.baseline = baseline;
+    F.min_fold = min_fold;
+    F.min_freq = min_freq;
+    F.max_freq = max_freq;
+    F.ratio = ratio;
+    hipError_t e = hipMemcpyAsync((void *)F.set_off, set_off, (size_t)(n_sets + 1) * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)F.unit_off, unit_off, (size_t)(n_units + 1) * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess && n_uc) e = hipMemcpyAsync((void *)F.unit_chrom, unit_chrom, (size_t)n_uc * 4, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync((void *)F.unit_den, den, (size_t)n_units * 16, hipMemcpyHostToDevice, stream);
+    return e;
+}
 
 template <typename CNT>
 __device__ __forceinline__ void sp_filter_decide(CNT &&cnt, unsigned long long tot,

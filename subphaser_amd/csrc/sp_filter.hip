@@ -14,6 +14,7 @@
 // surviving rows, in ascending slot order, so the output is deterministic.
 #include "sp_device.h"
 #include "sp_filter.h"
+#include "sp_internal.h"
 
 #ifndef F_BLOCK
 #define F_BLOCK 256
@@ -513,9 +514,6 @@ k3_slow(const sp_tabref *__restrict__ tabs, sp_filter_params P, unsigned long lo
     }
 }
 
-// scan defined in sp_count.hip
-__global__ void scan_excl_u64(unsigned long long *a, int64_t n, unsigned long long *total);
-
 // Pass B, step 1: ordered list of the surviving slots (bitmap walk only; the table gathers of a row used to
 // run on the one lane that owned its slot -- one active lane per wave at 0.4 % density)
 __global__ void __launch_bounds__(F_BLOCK)
@@ -617,11 +615,6 @@ static int upload_tabs(sp_ctx *ctx, const sp_tabref **d_tabs, double **d_len) {
     *d_len = (double *)((char *)scr + C * sizeof(sp_tabref));
     return SP_OK;
 }
-
-int sp_sparse_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off,
-                     const int32_t *unit_chrom, const std::vector<double> &den, double min_fold, int baseline,
-                     double min_freq, double max_freq, double ratio);                      // sp_sparse.hip
-int sp_sparse_fetch(sp_ctx *ctx, bool hist, uint64_t *keys, uint32_t *counts, double *freqs, uint64_t *tot, bool async);
 
 extern "C" {
 
@@ -744,35 +737,32 @@ int sp_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *un
         den[(size_t)u] = (double)d;
         den[(size_t)(n_units + u)] = 1.0 / (double)d;
     }
-    size_t b_set = (size_t)(n_sets + 1) * 4, b_uo = (size_t)(n_units + 1) * 4, b_uc = (size_t)(n_uc > 0 ? n_uc : 1) * 4,
-           b_den = (size_t)n_units * 16;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t tot_b = al(b_set) + al(b_uo) + al(b_uc) + al(b_den) + al(C * sizeof(sp_tabref)) + 256;
-    int rcb = sp_buf_ensure(ctx, ctx->b_fpar, (int64_t)tot_b);
+    // b_fpar: the set structure | table references | [0] union count, [1..2] scan totals
+    const size_t uc_room = (size_t)(n_uc > 0 ? n_uc : 1);
+    char *d_fs = nullptr;
+    sp_tabref *d_tabs = nullptr;
+    unsigned long long *d_nuni = nullptr;
+    auto lay = [&](sp_carve cv) {
+        d_fs = cv.take<char>(sp_fsets_bytes(n_sets, n_units, uc_room));
+        d_tabs = cv.take<sp_tabref>((size_t)C);
+        d_nuni = cv.take<unsigned long long>(32);
+        return cv.off;
+    };
+    int rcb = sp_buf_ensure(ctx, ctx->b_fpar, (int64_t)lay(sp_carve()));
     if (rcb) return rcb;
-    char *d_par = (char *)ctx->b_fpar.p;
-    char *p = d_par;
-    int32_t *d_set = (int32_t *)p; p += al(b_set);
-    int32_t *d_uo = (int32_t *)p; p += al(b_uo);
-    int32_t *d_uc = (int32_t *)p; p += al(b_uc);
-    double *d_den = (double *)p; p += al(b_den);
-    sp_tabref *d_tabs = (sp_tabref *)p; p += al(C * sizeof(sp_tabref));
-    unsigned long long *d_nuni = (unsigned long long *)p;   // [0] union count, [1..2] scan totals
+    lay(sp_carve(ctx->b_fpar.p));
     std::vector<sp_tabref> htabs((size_t)C);
     for (int i = 0; i < C; i++) htabs[(size_t)i] = filter_tab(ctx, i);
-    hipError_t e = hipSuccess;
-    auto cp = [&](void *d, const void *h, size_t n) {
-        if (e == hipSuccess && n) e = hipMemcpyAsync(d, h, n, hipMemcpyHostToDevice, ctx->stream);
-    };
-    cp(d_set, set_off, b_set);
-    cp(d_uo, unit_off, b_uo);
-    cp(d_uc, unit_chrom, (size_t)n_uc * 4);
-    cp(d_den, den.data(), b_den);
-    cp(d_tabs, htabs.data(), C * sizeof(sp_tabref));
+    sp_fsets F;
+    hipError_t e = sp_fsets_upload(ctx->stream, d_fs, n_sets, set_off, unit_off, unit_chrom, uc_room, den.data(), min_fold,
+                                   baseline, min_freq, max_freq, ratio, F);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_tabs, htabs.data(), (size_t)C * sizeof(sp_tabref), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess) e = hipMemsetAsync(d_nuni, 0, 32, ctx->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // host staging vectors go out of scope
     if (e != hipSuccess)
         return sp_fail(ctx, SP_EHIP, "sp_filter: parameter upload failed: %s", hipGetErrorString(e));
+    const int32_t *d_set = F.set_off, *d_uo = F.unit_off, *d_uc = F.unit_chrom;
+    const double *d_den = F.unit_den;
     sp_filter_params P;
     P.C = C;
     P.n_sets = n_sets;

@@ -1,0 +1,49 @@
+// sp_internal.h -- every host function and kernel that one translation unit defines and another one calls.  The unit
+// that defines a function includes this header as its callers do, so a declaration cannot drift from its definition.
+// (Kernels launched from another unit go through their host stubs: no relocatable device code.)
+#pragma once
+#include "sp_common.h"
+
+struct c2_bdesc;         // sp_c2batch.h
+struct sp_map_params;    // sp_map.h
+
+// sp_ctx.hip
+__global__ void k0_pack(const uint8_t *ascii, int64_t len, uint32_t *pk, uint32_t *pm, uint32_t *nm, int64_t n_mask_words);
+
+// sp_count.hip
+__global__ void scan_excl_u64(unsigned long long *a, int64_t n, unsigned long long *total);
+int sp_ovf_finalize(sp_ctx *ctx, sp_chrom &c, const uint2 *tmp, const uint32_t *seg_base, const uint32_t *seg_cnt,
+                    uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total);
+int sp_ovf_finalize_split(sp_ctx *ctx, unsigned long long *keys, uint32_t *cnts, const uint2 *tmp, const uint32_t *seg_base,
+                          const uint32_t *seg_cnt, uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total);
+int sp_ovf_finalize_split_batch(sp_ctx *ctx, const c2_bdesc *d_desc, int n_chrom, int64_t n_buckets);
+
+// sp_count2.hip
+bool sp_engine2_supported(int64_t nslots);
+int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower, unsigned long long *d_len4, bool exact,
+                     sp_sparse_chrom *list);
+int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kparams &kp, int lower, unsigned long long *d_len);
+
+// sp_sparse.hip: count engine 1 of k > 15, the label tables and the map kernels of k > 15
+void sp_sparse_release(sp_ctx *ctx);
+int sp_sparse_count(sp_ctx *ctx, int k, int lower);
+int sp_sparse_dump(sp_ctx *ctx, int chrom, uint64_t *keys, uint32_t *counts);
+int sp_sparse_labels_set(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, bool on_device);
+int sp_sparse_map_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n);
+int sp_sparse_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
+                          const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts);
+int sp_sparse_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, const unsigned long long *d_cov,
+                          unsigned long long *d_masks);
+int sp_sparse_hit(sp_ctx *ctx, unsigned long long *d_n);
+
+// sp_sparse2.hip
+int sp_sparse_count3(sp_ctx *ctx, int k, int lower);
+
+// sp_listfilter.hip
+int sp_sparse_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int32_t *unit_off, const int32_t *unit_chrom,
+                     const std::vector<double> &den, double min_fold, int baseline, double min_freq, double max_freq,
+                     double ratio);
+int sp_sparse_fetch(sp_ctx *ctx, bool hist, uint64_t *keys, uint32_t *counts, double *freqs, uint64_t *tot, bool async);
+
+// sp_map.hip
+int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n);

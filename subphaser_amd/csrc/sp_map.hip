@@ -4,6 +4,7 @@
 // (reference: subphaser/Seqs.py:74-153, 209-244): every k-mer START position
 // whose canonical k-mer is subgenome-specific adds 1 to (bin of start, SG).
 #include "sp_device.h"
+#include "sp_internal.h"
 #include "sp_map.h"
 
 // ----------------------------------------------------------------- K4
@@ -872,17 +873,12 @@ k4_count_seen(const uint8_t *__restrict__ label, int64_t nslots, unsigned long l
     if (threadIdx.x == 0 && t) atomicAdd(out, t);
 }
 
-// pack kernel from sp_ctx.hip
-__global__ void k0_pack(const uint8_t *ascii, int64_t len, uint32_t *pk, uint32_t *pm, uint32_t *nm, int64_t n_mask_words);
-
 static int64_t map_nslots_host(int64_t len, int64_t bin_size, int64_t chunk_size, int k) {
     int64_t L = len > 0 ? len : 1;
     int64_t nb = (L + bin_size - 1) / bin_size;
     int64_t nch = chunk_size > 0 ? (L + (k - 1)) / chunk_size + 1 : 1;
     return nb + nch;
 }
-
-int sp_sparse_labels_set(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, bool on_device);   // sp_sparse.hip
 
 // the flags of one sp_labels_set call -> page-locked host memory the kernel writes directly: a hipMemcpy of 32 bytes
 // would queue on the copy engine behind the matrix rows that are still travelling to the host (2 ms per pass)
@@ -917,12 +913,6 @@ k4_label_max(const uint8_t *__restrict__ sg, int64_t n, unsigned int *__restrict
     }
     if ((threadIdx.x & 63) == 0 && m) atomicMax(out, m);
 }
-int sp_sparse_map_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n);
-int sp_sparse_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
-                          const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts);
-int sp_sparse_hit(sp_ctx *ctx, unsigned long long *d_n);
-int sp_sparse_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, const unsigned long long *d_cov,
-                          unsigned long long *d_masks);
 
 // Build the pair filter over the labelled keys (device array, canonical 2-bit keys) at the smallest
 // size whose fill stays below MAP_FILL_MAX.  Shared by the dense and the sparse label paths.
@@ -1319,9 +1309,6 @@ int sp_stack_windows(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, int64_t 
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SP_OK;
 }
-
-int sp_enrich_dev(sp_ctx *ctx, const void *d_counts, int64_t W, int S, double max_pval, double min_ratio, double *pvals,
-                  int32_t *argmin, uint8_t *sig, double *ratios);   // sp_enrich.hip
 
 // map -> stack -> enrich without leaving the device: the window table is built in HBM, the column totals are
 // reduced there, every window row (empty ones included: they change no total) is tested, and the table and the

@@ -24,6 +24,7 @@
 // chromosome at k = 21) are sorted together by one segmented device sort and run-length encoded by s3_big_rle.
 // Bytes per key (k = 21): 0.375 x 3 scans + 4 w + 4 r + 4 r + 4 w + 4 r  ~ 21 B against ~100 B.
 #include "sp_device.h"
+#include "sp_internal.h"
 
 #define S3_MAXF 1024
 #define S3_P1_UNIT 32

@@ -5,7 +5,7 @@
 # out of a loop as 64-bit lane masks runs out of SGPRs and pays two v_readlane per test at every use.
 #   tools/isa_survey.sh [unit ...]     (default: every unit of the library)   ->  one table on stdout
 cd "$(dirname "$0")/../subphaser_amd/csrc" || exit 1
-UNITS=${@:-sp_count sp_count2 sp_filter sp_map sp_sparse_all sp_enrich sp_fasta sp_text sp_synth sp_ctx}
+UNITS=${@:-sp_count sp_count2 sp_filter sp_map sp_sparse_all sp_listfilter sp_enrich sp_fasta sp_text sp_synth sp_ctx}
 FLAGS="-O3 -std=c++17 -fPIC --offload-arch=gfx950 -fno-fast-math -ffp-contract=off -Wno-unused-value -Wno-unused-result -Wno-unused-function"
 T=$(mktemp -d)
 printf "%-34s %5s %5s %7s %7s %7s %9s %9s\n" kernel vgpr sgpr scratch instr valu "rd/wrlane" "behind-1st-loop-header"
