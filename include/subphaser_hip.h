@@ -251,6 +251,22 @@ int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, co
                        const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                        double *pvals, double *means);
 
+/* ---- bootstrap support of the chromosome -> subgenome assignment -----------------------------
+ * Replaces the loop of Cluster.bootstrap (Cluster.py:82-118): R k-means fits, replicate r on the n columns
+ * cols[r * n .. r * n + n) of z (C x M row-major fp64, the Z-normalised matrix; every index in [0, M), checked before
+ * anything is launched: SP_EINVAL).  One workgroup per replicate: it gathers its columns, accumulates the C x C Gram
+ * matrix in draw order (bit-defined), and runs greedy k-means++ and Lloyd on it (csrc/sp_kboot.h states every order
+ * and the counter-based RNG; `seed` selects the stream, the replicate index the substream).  The reference's fits are
+ * unseeded, so its support column is a random variable; this draws from the same distribution.
+ * labels: R x C raw cluster ids in [0, K) (the caller renumbers them by chromosome order); iters: Lloyd iterations per
+ * replicate (at most 300); gram: R x C x C, filled when not NULL (for tests).
+ * Limits: 1 <= K <= C and n >= 1 (SP_EINVAL otherwise); C <= 128 and K <= 32 (SP_EUNSUP beyond: the caller keeps
+ * scikit-learn).  `z` may also be a device pointer (staged with sp_dev_copy_from_host earlier); a host matrix is
+ * uploaded for the call and released after it (SP_ENOMEM with the size when it does not fit).                     */
+int sp_kmeans_bootstrap(sp_ctx *ctx, const double *z /*C x M*/, int C, int64_t M, const int64_t *cols /*R x n*/, int R,
+                        int n, int K, uint64_t seed, int32_t *labels /*R x C*/, int32_t *iters /*R*/,
+                        double *gram /*R x C x C or NULL*/);
+
 /* ---- multi-GPU, k > 15 ----------------------------------------------------------------------
  * Twin of sp_tables_bind / sp_filter_view for 64-bit keys ("for k > 16 the exchange
  * becomes key-partitioned").  After sp_count (k > 15) every local chromosome is a sorted list of

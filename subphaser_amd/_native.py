@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SUBPHASER_HIP_LIB") or os.path.join(_HERE, "lib", "libsubphaser_hip.so")
 
 SP_OK, SP_EINVAL, SP_EUNSUP, SP_ENOMEM, SP_EHIP, SP_ENODEV, SP_ESTATE, SP_EIO = 0, -1, -2, -3, -4, -5, -6, -7
+KBOOT_MAX_POINTS, KBOOT_MAX_CLUSTERS = 128, 32     # SP_KB_MAXC, SP_KB_MAXK in csrc/sp_kboot.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -23,7 +24,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -112,6 +113,7 @@ def load():
     L.sp_enrich_dev.argtypes = [vp, vp, i64, ci, dbl, dbl, vp, vp, vp, vp]
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -780,6 +782,32 @@ class Context:
         self._ck(entry(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
                        _p(top), _p(second), _p(pvals), _p(means)))
         return top, second, pvals, means
+
+    def kmeans_bootstrap(self, z, cols, K, seed, want_gram=False):
+        """Cluster.bootstrap's k-means fits on the device (sp_kmeans_bootstrap): replicate r clusters the C rows of z
+        (float64 [C, M], the Z-normalised matrix) over the columns cols[r] (int64 [R, n]) into K clusters; `seed`
+        (64 bits) selects the stream of its k-means++ draws.  Returns (labels int32 [R, C], raw cluster ids; iters
+        int32 [R]) and, with want_gram, the Gram matrices float64 [R, C, C] the fits ran on.
+        C <= KBOOT_MAX_POINTS and K <= KBOOT_MAX_CLUSTERS (ValueError beyond, as for K > C or an index outside [0, M)).
+        z may also be (device pointer, C, M): a matrix copied to the device earlier (dev_alloc / host_to_dev)."""
+        if isinstance(z, tuple):
+            d_ptr, Cn, M = z
+            zptr = C.c_void_p(int(d_ptr))
+        else:
+            z = np.ascontiguousarray(z, np.float64)
+            if z.ndim != 2:
+                raise ValueError("z must be C x M")
+            Cn, M = z.shape
+            zptr = _p(z)
+        cols = np.ascontiguousarray(cols, np.int64)
+        if cols.ndim != 2:
+            raise ValueError("cols must be R x n")
+        R, n = cols.shape
+        labels, iters = np.empty((R, Cn), np.int32), np.empty(R, np.int32)
+        gram = np.empty((R, Cn, Cn), np.float64) if want_gram else None
+        self._ck(self.L.sp_kmeans_bootstrap(self.h, zptr, int(Cn), int(M), _p(cols), R, n, int(K),
+                                            C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _p(labels), _p(iters), _p(gram)))
+        return (labels, iters, gram) if want_gram else (labels, iters)
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

@@ -6,10 +6,12 @@ produces the input of the second half of the hot path:
   Cluster.__init__/fit/sort_subgenomes/assign_subgenomes (Cluster.py:17-47, 114-143)
   Cluster.output_kmers / _output_kmers                    (Cluster.py:151-194)
 so that an end-to-end run is self-contained.  KMeans is delegated to
-scikit-learn exactly like the reference; bootstrap and PCA plots stay with the
-reference (visualisation, out of scope).  The per-k-mer Student t-test is
+scikit-learn exactly like the reference; the bootstrap's k-means fits can also
+run on the device (bootstrap_engine="device": csrc/sp_kboot.hip); PCA plots stay
+with the reference (visualisation, out of scope).  The per-k-mer Student t-test is
 vectorised over the M x C matrix instead of looped through a process pool.
 """
+import os
 import sys
 from collections import OrderedDict
 
@@ -57,8 +59,13 @@ class Cluster:
     bootstrap support and the subgenome-specific k-mer test."""
 
     def __init__(self, data, n_clusters, sg_prefix="SG", sg_assigned={}, re_assign=True, bootstrap=False,
-                 replicates=1000, jackknife=80, seed=None, **kargs):
-        """data: path of a `.kmer.mat` file or a FilteredMatrix (jellyfish.filter result)."""
+                 replicates=1000, jackknife=80, seed=None, bootstrap_engine="sklearn", **kargs):
+        """data: path of a `.kmer.mat` file or a FilteredMatrix (jellyfish.filter result).
+        bootstrap_engine: "sklearn" (the loop of scikit-learn fits) or "device" (Context.kmeans_bootstrap: up to
+        KBOOT_MAX_POINTS chromosomes in KBOOT_MAX_CLUSTERS clusters, the scikit-learn loop beyond)."""
+        if bootstrap_engine not in BOOTSTRAP_ENGINES:
+            raise ValueError("bootstrap_engine must be one of {}".format(BOOTSTRAP_ENGINES))
+        self.bootstrap_engine = bootstrap_engine
         if isinstance(data, str):
             self.chrs, kmers, self.raw_data = load_matrix(data)
             self.k = len(kmers[0]) if kmers else 0
@@ -112,12 +119,54 @@ class Cluster:
         z = self.zscores()                                   # C x M
         rng = np.random.RandomState(self.seed)
         M = z.shape[1]
-        agree = np.zeros(len(self.chrs), np.int64)
-        for _ in range(int(replicates)):
-            cols = rng.randint(0, M, size=int(replicates))
-            rep = relabel_by_chromosome_order(self.chrs, self._kmeans(z[:, cols]).labels_)
-            agree += rep == self.labels
+        R = int(replicates)
+        entry = self._device_bootstrap(z) if self.bootstrap_engine == "device" else None
+        if entry is not None:
+            # the columns exactly as the loop below draws them: a given seed resamples the same k-mers under both engines
+            cols = np.array([rng.randint(0, M, size=R) for _ in range(R)], np.int64).reshape(R, R)
+            seed = self.seed if self.seed is not None else int.from_bytes(os.urandom(8), "little")
+            raw, _ = entry(z, cols, self.n_clusters, seed)
+            reps = np.array([relabel_by_chromosome_order(self.chrs, r) for r in raw], np.int64).reshape(R, len(self.chrs))
+        else:
+            reps = np.empty((R, len(self.chrs)), np.int64)
+            for i in range(R):
+                cols = rng.randint(0, M, size=R)
+                reps[i] = relabel_by_chromosome_order(self.chrs, self._kmeans(z[:, cols]).labels_)
+        self.bootstrap_labels = reps                         # R x C, renumbered by chromosome order
+        agree = (reps == self.labels[None, :]).sum(axis=0)
+        self._bootstrap_scores(reps)
         return {c: int(100 * a / replicates) for c, a in zip(self.chrs, agree.tolist())}
+
+    def _device_bootstrap(self, z):
+        """Context.kmeans_bootstrap when the device engine applies, else None (one log line says why)"""
+        entry = getattr(getattr(self, "_ctx", None), "kmeans_bootstrap", None)
+        C, K = z.shape[0], self.n_clusters
+        if entry is None:
+            why = "no device context with the k-means bootstrap"
+        elif C > _native.KBOOT_MAX_POINTS or K > _native.KBOOT_MAX_CLUSTERS:
+            why = "{} chromosomes in {} clusters (the device engine takes up to {} in {})".format(
+                C, K, _native.KBOOT_MAX_POINTS, _native.KBOOT_MAX_CLUSTERS)
+        elif K > C:
+            why = "{} clusters for {} chromosomes".format(K, C)
+        else:
+            if not np.isfinite(z).all():
+                raise ValueError("Input contains NaN or infinity: the Z-normalised matrix of the bootstrap")
+            return entry
+        logger.info("bootstrap_engine=device: {}; using scikit-learn".format(why))
+        return None
+
+    def _bootstrap_scores(self, reps):
+        """the reference's log line (Cluster.py:108-111): every replicate's labels against the assignment"""
+        from sklearn import metrics
+        truth = self.labels
+        # most replicates repeat a few label vectors: one pair of scores per distinct vector, weighted by its count
+        # (a millisecond per score otherwise: as long as the fits themselves at 1000 replicates)
+        uniq, counts = np.unique(reps, axis=0, return_counts=True)
+        w = counts / float(len(reps))
+        self.mean_adjusted_rand_score = float(np.dot(w, [metrics.adjusted_rand_score(truth, r) for r in uniq]))
+        self.mean_v_measure_score = float(np.dot(w, [metrics.v_measure_score(truth, r) for r in uniq]))
+        logger.info("Bootstrap: mean Adjusted Rand-Index: {:.4f}; mean V-measure score: {:.4f}".format(
+            self.mean_adjusted_rand_score, self.mean_v_measure_score))
 
     def output_subgenomes(self, fout=sys.stdout):
         fout.write("#chrom\tsubgenome\tbootstrap\n")
@@ -191,6 +240,7 @@ class Cluster:
 
 
 TEST_METHODS = ("ttest_ind", "kruskal", "wilcoxon", "mannwhitneyu")
+BOOTSTRAP_ENGINES = ("sklearn", "device")
 TTEST_MAX_GROUP = 64     # SP_TT_MAXG in csrc/sp_enrich.hip
 TTEST_WIDE_MAX_GROUP = 65536     # SP_TT_WIDE_MAX in csrc/sp_ttest.h
 

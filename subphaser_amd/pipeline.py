@@ -22,7 +22,7 @@ import numpy as np
 
 from . import REFERENCE_VERSION, __version__
 from . import circos, seqs, stats
-from .cluster import TEST_METHODS, Cluster
+from .cluster import BOOTSTRAP_ENGINES, TEST_METHODS, Cluster
 from .config import SGConfig, check_duplicates, parse_idmap
 from .jellyfish import JellyfishDumps, plot_histogram, run_jellyfish_dumps
 from .runtime import get_context, logger
@@ -99,6 +99,11 @@ CLI = [
         (("-engine",), dict(type=int, default=0, help="k-mer counting engine (0 auto, 1 atomic table, 2 LDS radix, 3 LDS radix into lists: small genomes)")),
         (("-write_dumps",), dict(help="also write jellyfish-style text dumps {chrom}_{k}.fa", **_FLAG)),
         (("-bootstrap_seed",), dict(type=int, default=None, help="seed of k-means and of the bootstrap resampling")),
+        (("-bootstrap_engine",), dict(choices=list(BOOTSTRAP_ENGINES), default="sklearn",
+                                      help="k-means fits of the bootstrap: sklearn (the reference's loop of scikit-learn fits) or "
+                                           "device (one kernel launch, greedy k-means++ and Lloyd per replicate; up to 128 "
+                                           "chromosomes in 32 subgenomes, the scikit-learn loop beyond; the same -bootstrap_seed "
+                                           "resamples the same k-mers under both)")),
     ]),
 ]
 
@@ -345,7 +350,8 @@ class Pipeline:
     def stage_cluster(self, lay, d_mat2, assigned):
         logger.info("###Step: Cluster")
         cl = Cluster(d_mat2, n_clusters=self.nsg, sg_prefix="SG", sg_assigned=assigned, bootstrap=True,
-                     replicates=self.replicates, jackknife=self.jackknife, seed=self.bootstrap_seed)
+                     replicates=self.replicates, jackknife=self.jackknife, seed=self.bootstrap_seed,
+                     bootstrap_engine=getattr(self, "bootstrap_engine", "sklearn"))
         logger.info("Subgenome assignments: {}".format(dict(cl.d_sg)))
         with open(lay.out("chrom-subgenome.tsv"), "w") as fout:
             cl.output_subgenomes(fout)

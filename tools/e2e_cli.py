@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """End-to-end wall clock of the `subphaser` CLI (modules 1-2) on a synthetic genome written to disk as
 FASTA: FASTA in the page cache -> every output file on disk.  Reported separately from bench.py's
-device-resident throughput.  usage: e2e_cli.py [config=ara] [workdir=/tmp/sp_e2e]"""
+device-resident throughput.  usage: e2e_cli.py [config=ara] [workdir=/tmp/sp_e2e]
+SP_E2E_ARGS: further CLI options, e.g. "-bootstrap_engine device"."""
 import os, subprocess, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -37,7 +38,7 @@ print("synthetic FASTA: %.1f MB written in %.1f s" % (os.path.getsize(fa) / 1e6,
 prof = ["-m", "cProfile", "-o", os.path.join(work, "cli.prof")] if os.environ.get("SP_E2E_PROFILE") else []
 cmd = [sys.executable] + prof + ["-m", "subphaser_amd", "-i", fa, "-c", os.path.join(work, "sg.config"), "-sg_assigned",
        os.path.join(work, "assigned.tsv"), "-o", os.path.join(work, "out"), "-tmpdir", os.path.join(work, "tmp"),
-       "-disable_ltr", "-disable_circos", "-overwrite", "-figfmt", "png"]
+       "-disable_ltr", "-disable_circos", "-overwrite", "-figfmt", "png"] + os.environ.get("SP_E2E_ARGS", "").split()
 t0 = time.perf_counter()
 # the CLI's log lines are stamped as they ARRIVE (its own timestamps have one-second resolution): the per-phase wall table
 proc = subprocess.Popen(cmd, cwd=ROOT, stdout=subprocess.DEVNULL, stderr=subprocess.PIPE, text=True, bufsize=1,
