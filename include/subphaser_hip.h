@@ -267,6 +267,26 @@ int sp_kmeans_bootstrap(sp_ctx *ctx, const double *z /*C x M*/, int C, int64_t M
                         int n, int K, uint64_t seed, int32_t *labels /*R x C*/, int32_t *iters /*R*/,
                         double *gram /*R x C x C or NULL*/);
 
+/* ---- PCA of the k-mer matrix (Cluster.pca, Cluster.py:48-75) -------------------------------------------------
+ * sklearn's PCA of the C x M Z-score matrix, split where the work is: the two passes over the M rows run here, the
+ * C x C eigen-decomposition between them on the host.  counts / lengths as in sp_kmer_ttest (counts a host or a device
+ * pointer: rows staged on this device are read in place, host rows are uploaded for the call and released after it).
+ * Z is never materialised; csrc/sp_kpca.h states every order of operations, and both results are bit-defined.
+ * sp_kmer_pca_gram: kp_rowstats writes (mean, sd) of every row -- x = count / length, sums left to right, population
+ * variance -- and counts the bad rows (sd == 0 or not finite) into *n_bad; kp_gram accumulates, per tile of chromosome
+ * pairs and per chunk of SP_KP_ROWS = 1024 rows, the products z_a z_b of the good rows in row order; kp_gram_sum adds the
+ * chunks in chunk order and mirrors the triangle into gram (C x C).  stats: M x 2 (mean, sd), filled when not NULL (for
+ * tests).  Workspace: chunks x C (C + 1) / 2 x 8 + M x 16 bytes, checked before any launch (SP_ENOMEM with its size).
+ * sp_kmer_pca_signs: for each of the n_comp columns of U (C x n_comp row-major, the eigenvectors) the good row with the
+ * largest |v_j| = |sum_c U[c][j] z_c| (left to right), the lowest row on ties: rows[j] its index, vals[j] the signed
+ * v_j; (-1, 0) when every row is bad.  It recomputes the row statistics: the call stands alone and does not depend on a
+ * preceding sp_kmer_pca_gram.
+ * SP_EINVAL: C < 2, M < 1, n_comp outside 1..32, a length <= 0.  SP_EUNSUP: C > 1024.                              */
+int sp_kmer_pca_gram(sp_ctx *ctx, const uint32_t *counts /*M x C, host or device*/, int64_t M, int C,
+                     const int64_t *lengths, double *gram /*C x C*/, int64_t *n_bad, double *stats /*M x 2 or NULL*/);
+int sp_kmer_pca_signs(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths,
+                      const double *U /*C x n_comp*/, int n_comp, int64_t *rows /*n_comp*/, double *vals /*n_comp*/);
+
 /* ---- multi-GPU, k > 15 ----------------------------------------------------------------------
  * Twin of sp_tables_bind / sp_filter_view for 64-bit keys ("for k > 16 the exchange
  * becomes key-partitioned").  After sp_count (k > 15) every local chromosome is a sorted list of

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get("SUBPHASER_HIP_LIB") or os.path.join(_HERE, "lib", "li
 
 SP_OK, SP_EINVAL, SP_EUNSUP, SP_ENOMEM, SP_EHIP, SP_ENODEV, SP_ESTATE, SP_EIO = 0, -1, -2, -3, -4, -5, -6, -7
 KBOOT_MAX_POINTS, KBOOT_MAX_CLUSTERS = 128, 32     # SP_KB_MAXC, SP_KB_MAXK in csrc/sp_kboot.h
+KPCA_MAX_CHROM, KPCA_MAX_COMP = 1024, 32           # SP_KP_MAXC, SP_KP_MAXCOMP in csrc/sp_kpca.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -24,7 +25,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -114,6 +115,8 @@ def load():
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
+    L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
+    L.sp_kmer_pca_signs.argtypes = [vp, vp, i64, ci, vp, vp, ci, vp, vp]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -808,6 +811,45 @@ class Context:
         self._ck(self.L.sp_kmeans_bootstrap(self.h, zptr, int(Cn), int(M), _p(cols), R, n, int(K),
                                             C.c_uint64(int(seed) & 0xFFFFFFFFFFFFFFFF), _p(labels), _p(iters), _p(gram)))
         return (labels, iters, gram) if want_gram else (labels, iters)
+
+    @staticmethod
+    def _rows_arg(counts):
+        if isinstance(counts, tuple):
+            d_ptr, M, Cn = counts
+            return None, C.c_void_p(int(d_ptr)), int(M), int(Cn)
+        counts = np.ascontiguousarray(counts, np.uint32)
+        if counts.ndim != 2:
+            raise ValueError("counts must be M x C")
+        return counts, _p(counts), counts.shape[0], counts.shape[1]
+
+    def kmer_pca_gram(self, counts, lengths, want_stats=False):
+        """The pass of Cluster.pca over the k-mers (sp_kmer_pca_gram): counts uint32 [M, C] or (device pointer, M, C) as
+        stage_rows returns it, lengths int64 [C].  Returns (gram float64 [C, C], the Gram matrix of the Z-scores over the
+        good rows, bit-defined by csrc/sp_kpca.h; n_bad, the rows whose standard deviation is 0) and, with want_stats,
+        the (mean, sd) of every row, float64 [M, 2].  2 <= C <= KPCA_MAX_CHROM, M >= 1 (ValueError otherwise)."""
+        keep, cptr, M, Cn = self._rows_arg(counts)
+        lengths = np.ascontiguousarray(lengths, np.int64)
+        if lengths.shape != (Cn,):
+            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
+        gram = np.empty((Cn, Cn), np.float64)
+        stats = np.empty((M, 2), np.float64) if want_stats else None
+        n_bad = C.c_int64()
+        self._ck(self.L.sp_kmer_pca_gram(self.h, cptr, M, Cn, _p(lengths), _p(gram), C.byref(n_bad), _p(stats)))
+        return (gram, n_bad.value, stats) if want_stats else (gram, n_bad.value)
+
+    def kmer_pca_signs(self, counts, lengths, U):
+        """Per column j of U (float64 [C, n_comp], n_comp <= KPCA_MAX_COMP) the good row with the largest |U[:, j] . z|,
+        the lowest index on ties (sp_kmer_pca_signs): returns (rows int64 [n_comp], vals float64 [n_comp], the signed
+        projections there); (-1, 0) when every row is bad.  counts and lengths as in kmer_pca_gram."""
+        keep, cptr, M, Cn = self._rows_arg(counts)
+        lengths = np.ascontiguousarray(lengths, np.int64)
+        U = np.ascontiguousarray(U, np.float64)
+        if lengths.shape != (Cn,) or U.ndim != 2 or U.shape[0] != Cn:
+            raise ValueError("lengths must be [C] and U [C, n_comp] for C = {}".format(Cn))
+        n_comp = U.shape[1]
+        rows, vals = np.empty(n_comp, np.int64), np.empty(n_comp, np.float64)
+        self._ck(self.L.sp_kmer_pca_signs(self.h, cptr, M, Cn, _p(lengths), _p(U), n_comp, _p(rows), _p(vals)))
+        return rows, vals
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

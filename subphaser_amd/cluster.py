@@ -7,9 +7,12 @@ produces the input of the second half of the hot path:
   Cluster.output_kmers / _output_kmers                    (Cluster.py:151-194)
 so that an end-to-end run is self-contained.  KMeans is delegated to
 scikit-learn exactly like the reference; the bootstrap's k-means fits can also
-run on the device (bootstrap_engine="device": csrc/sp_kboot.hip); PCA plots stay
-with the reference (visualisation, out of scope).  The per-k-mer Student t-test is
-vectorised over the M x C matrix instead of looped through a process pool.
+run on the device (bootstrap_engine="device": csrc/sp_kboot.hip).  The k-mer PCA
+(Cluster.pca, Cluster.py:48-75: `.kmer_pca` coordinates and figure) is scikit-learn's
+full-solver PCA restated on the C x C Gram matrix of the Z-scores: the passes over the
+k-mers run on the device from the integer rows (csrc/sp_kpca.hip) or in numpy, the
+eigen-decomposition on the host.  The per-k-mer Student t-test is vectorised over the
+M x C matrix instead of looped through a process pool.
 """
 import os
 import sys
@@ -168,6 +171,75 @@ class Cluster:
         logger.info("Bootstrap: mean Adjusted Rand-Index: {:.4f}; mean V-measure score: {:.4f}".format(
             self.mean_adjusted_rand_score, self.mean_v_measure_score))
 
+    def pca(self, outfig=None, outtsv=None, n_components=2, colors=None, defer=False):
+        """The reference's k-mer PCA (Cluster.py:48-75) with the arithmetic of PCA(svd_solver="full"): the Gram matrix
+        G = Z Z^T of the C x M Z-scores, eigh(G) with the eigenvalues descending, scores U sqrt(w), every component
+        given the sign of its largest-|v| k-mer (v = u^T Z: scikit-learn's svd_flip), percent = 100 w / sum(w), then the
+        per-component Z-normalisation of the scores.  n = min(max(2, n_components), C) components are kept.
+        The two passes over the k-mers run on the device when the matrix came with a context that has the entries, the
+        integer counts and lengths, and C <= KPCA_MAX_CHROM (staged rows are read in place); in numpy on zscores()
+        otherwise (one log line says which).  A k-mer whose Z-scores are not finite raises ValueError, as scikit-learn
+        would.  Keeps pca_scores [C, n], pca_percent [n] and pca_engine ("device" / "numpy").
+        outtsv: `#PC1=..%` line, header, one row per chromosome in matrix order, floats written with repr.
+        outfig: the reference's scatter (one colour per subgenome; `colors`: a list or a comma-separated string of
+        colours, matplotlib's cycle otherwise); skipped with a warning when matplotlib is missing.
+        defer=True: the figure is not drawn; returns write() that draws it later (the CLI's main-thread writer queue)."""
+        C = len(self.chrs)
+        ctx = getattr(self, "_ctx", None)
+        gram_entry, sign_entry = getattr(ctx, "kmer_pca_gram", None), getattr(ctx, "kmer_pca_signs", None)
+        counts, lengths = getattr(self, "_counts", None), getattr(self, "_lengths", None)
+        if gram_entry is None or sign_entry is None:
+            why = "no device context with the k-mer PCA"
+        elif counts is None or lengths is None:
+            why = "no integer counts behind the matrix"
+        elif C > _native.KPCA_MAX_CHROM:
+            why = "{} chromosomes (the device takes up to {})".format(C, _native.KPCA_MAX_CHROM)
+        else:
+            why = None
+        n = min(max(2, int(n_components)), C)
+        if why is None:
+            rows = getattr(self, "_counts_dev", None) or counts
+            logger.info("k-mer PCA: {} k-mers x {} chromosomes on the device{}".format(
+                len(self.raw_data), C, " (staged rows)" if rows is not counts else ""))
+            G, n_bad = gram_entry(rows, lengths)
+            sign_vals = lambda U: sign_entry(rows, lengths, U)[1]
+            self.pca_engine = "device"
+        else:
+            logger.info("k-mer PCA: {}; using numpy".format(why))
+            z = self.zscores()
+            n_bad = int((~np.isfinite(z)).any(axis=0).sum())
+            G = z @ z.T if not n_bad else None
+            def sign_vals(U):
+                v = U.T @ z
+                return v[np.arange(v.shape[0]), np.argmax(np.abs(v), axis=1)]
+            self.pca_engine = "numpy"
+        if n_bad:
+            raise ValueError("Input contains NaN or infinity: {} k-mers of the PCA have no finite Z-score "
+                             "(the same frequency on every chromosome)".format(n_bad))
+        w, V = np.linalg.eigh(G)
+        w, V = w[::-1], V[:, ::-1]
+        U = np.ascontiguousarray(V[:, :n])
+        sign = np.where(np.asarray(sign_vals(U)) < 0, -1.0, 1.0)
+        scores = U * np.sqrt(np.maximum(w[:n], 0.0)) * sign
+        self.pca_percent = 100 * w[:n] / w.sum()
+        with np.errstate(all="ignore"):
+            self.pca_scores = self.normalize_data(scores, axis=0)
+        if outtsv is not None:
+            with open(outtsv, "w") as fout:
+                fout.write("#" + "\t".join("PC{}={}%".format(j + 1, repr(float(p))) for j, p in enumerate(self.pca_percent)) + "\n")
+                fout.write("\t".join(["#chrom", "subgenome"] + ["PC{}".format(j + 1) for j in range(n)]) + "\n")
+                for c, row in zip(self.chrs, self.pca_scores.tolist()):
+                    fout.write("\t".join([c, self.d_sg[c]] + [repr(v) for v in row]) + "\n")
+        scores, percent = self.pca_scores, self.pca_percent
+        chrs, d_sg, labels = list(self.chrs), dict(self.d_sg), self.labels.tolist()
+
+        def write():
+            if outfig is not None:
+                plot_pca(outfig, scores, percent, chrs, d_sg, labels, colors)
+        if defer:
+            return write
+        write()
+
     def output_subgenomes(self, fout=sys.stdout):
         fout.write("#chrom\tsubgenome\tbootstrap\n")
         for c in sorted(self.d_sg, key=lambda x: self.d_sg[x]):      # stable: by subgenome, input order inside
@@ -237,6 +309,36 @@ class Cluster:
             return labels, write
         write(fout)
         return labels
+
+
+def plot_pca(outfig, scores, percent, chrs, d_sg, labels, colors=None):
+    """Same figure as Cluster.py:56-75 (visualisation; optional)."""
+    try:
+        from matplotlib import pyplot as plt
+    except ImportError:
+        logger.warning("matplotlib missing: skipping " + outfig)
+        return
+    plt.switch_backend("agg")
+    if isinstance(colors, str):
+        colors = colors.split(",")
+    if not colors:
+        colors = plt.rcParams["axes.prop_cycle"].by_key()["color"]
+    d_coord = {}
+    for x, y, c, l in zip(scores[:, 0].tolist(), scores[:, 1].tolist(), chrs, labels):
+        xs, ys, _ = d_coord.setdefault(d_sg[c], ([], [], colors[int(l) % len(colors)]))
+        xs.append(x)
+        ys.append(y)
+    fig = plt.figure(figsize=(7, 7), dpi=300, tight_layout=True)
+    for sg, (xs, ys, col) in sorted(d_coord.items()):
+        plt.scatter(xs, ys, c=col, marker="o", label=sg)
+    plt.axhline(0, ls="--", c="grey")
+    plt.axvline(0, ls="--", c="grey")
+    plt.xlabel("PC1 ({:.1f}%)".format(percent[0]), fontsize=18)
+    plt.ylabel("PC2 ({:.1f}%)".format(percent[1]), fontsize=18, ha="center", va="center")
+    plt.legend(fontsize=18)
+    plt.tick_params(labelsize=15)
+    plt.savefig(outfig, bbox_inches="tight", dpi=300)
+    plt.close(fig)
 
 
 TEST_METHODS = ("ttest_ind", "kruskal", "wilcoxon", "mannwhitneyu")

@@ -355,6 +355,7 @@ class Pipeline:
         logger.info("Subgenome assignments: {}".format(dict(cl.d_sg)))
         with open(lay.out("chrom-subgenome.tsv"), "w") as fout:
             cl.output_subgenomes(fout)
+        self._pca(lay, cl)      # before output_kmers: that releases the rows staged on the device
         sg_kmers = lay.out("sig.kmer-subgenome.tsv")
         logger.info("subgenome-specific k-mers -> `{}`".format(sg_kmers))
         t0 = time.perf_counter()
@@ -368,6 +369,35 @@ class Pipeline:
             if n:
                 logger.info("\t{} {}-specific kmers".format(n, sg))
         return cl, kmer_labels
+
+    def _pca(self, lay, cl):
+        """`.kmer_pca.tsv` and `.kmer_pca.<figfmt>` (__main__.py:467-469).  The coordinates are written here, the figure
+        with the background writers (drawn on the main thread, see _write_matrix_in_background).  Only non-finite input
+        stops the run, as it would stop scikit-learn; any other failure costs these two files and nothing else."""
+        if len(cl.chrs) < 2:
+            logger.info("k-mer PCA skipped: {} chromosome".format(len(cl.chrs)))
+            return
+        tsv, fig = lay.out("kmer_pca.tsv"), lay.out("kmer_pca." + self.figfmt)
+        t0 = time.perf_counter()
+        try:
+            draw = cl.pca(outfig=fig, outtsv=tsv, n_components=self.nsg or cl.n_clusters, colors=getattr(self, "colors", None),
+                          defer=True)
+        except Exception as e:
+            if isinstance(e, ValueError) and str(e).startswith("Input contains NaN or infinity"):
+                raise
+            logger.warning("k-mer PCA not written: {}".format(e))
+            return
+        mk_ckp(lay.ckp(tsv))
+        logger.info("k-mer PCA ({}) -> `{}` in {:.2f} s".format(cl.pca_engine, os.path.basename(tsv), time.perf_counter() - t0))
+
+        def done():
+            try:
+                draw()
+                if os.path.exists(fig):
+                    mk_ckp(lay.ckp(fig))
+            except Exception as e:     # the figure is optional
+                logger.warning("k-mer PCA not plotted: {}".format(e))
+        self._background.append((fig, lambda: None, done))
 
     # ---- stage 4: bin map -> window stack -> enrichment, on the device -----------------------------------
     def stage_windows(self, lay, chromfiles, labels, d_size, cl, kmer_labels):
