@@ -287,6 +287,22 @@ int sp_kmer_pca_gram(sp_ctx *ctx, const uint32_t *counts /*M x C, host or device
 int sp_kmer_pca_signs(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths,
                       const double *U /*C x n_comp*/, int n_comp, int64_t *rows /*n_comp*/, double *vals /*n_comp*/);
 
+/* ---- complete-linkage clustering for the heatmap (Cluster.heatmap, Jellyfish.py:524-609) ----------------------
+ * The dendrograms R's heatmap.2 draws over the sampled k-mers and over the chromosomes: Euclidean distances between the
+ * P rows of pts (host, P x D fp64, all finite) and the nearest-neighbour chain for complete linkage on them.
+ * csrc/sp_hclust.h states every order of operations and every tie rule, so merges is bit-defined: (P - 1) x 4 doubles,
+ * (slot x, slot y, height, size) in merge order with x < y, raw slot ids, unsorted -- what scipy's linkage holds before it
+ * sorts by height and relabels (subphaser_amd/heatmap.py: to_linkage).  hc_dist fills the P x P matrix in a device buffer
+ * (tiles of 32 x 32 pairs, coordinates staged through LDS 32 at a time, sums left to right, no FMA); hc_chain is ONE
+ * workgroup of 1024 threads that runs all P - 1 merges on it: no second workgroup, no cooperative launch, every loop
+ * bounded.  dist: the matrix before the first merge, P x P, filled when not NULL (for tests).
+ * SP_EINVAL: a NULL pointer, P < 2, D < 1, a coordinate that is not finite (checked on the host before any launch).
+ * SP_EUNSUP: P > 16384 (SP_HC_MAXP; decided before any allocation).  SP_ENOMEM: the workspace, P x P x 8 bytes and the
+ * points, does not fit.  SP_ESTATE: the chain passed 4 P scans or a point has no neighbour at a finite distance
+ * (squared differences that overflow).                                                                            */
+int sp_hclust_complete(sp_ctx *ctx, const double *pts /*host, P x D*/, int P, int D, double *merges /*(P-1) x 4*/,
+                       double *dist /*P x P or NULL*/);
+
 /* ---- multi-GPU, k > 15 ----------------------------------------------------------------------
  * Twin of sp_tables_bind / sp_filter_view for 64-bit keys ("for k > 16 the exchange
  * becomes key-partitioned").  After sp_count (k > 15) every local chromosome is a sorted list of

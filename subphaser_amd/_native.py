@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get("SUBPHASER_HIP_LIB") or os.path.join(_HERE, "lib", "li
 SP_OK, SP_EINVAL, SP_EUNSUP, SP_ENOMEM, SP_EHIP, SP_ENODEV, SP_ESTATE, SP_EIO = 0, -1, -2, -3, -4, -5, -6, -7
 KBOOT_MAX_POINTS, KBOOT_MAX_CLUSTERS = 128, 32     # SP_KB_MAXC, SP_KB_MAXK in csrc/sp_kboot.h
 KPCA_MAX_CHROM, KPCA_MAX_COMP = 1024, 32           # SP_KP_MAXC, SP_KP_MAXCOMP in csrc/sp_kpca.h
+HCLUST_MAX_POINTS = 16384                          # SP_HC_MAXP in csrc/sp_hclust.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -25,7 +26,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -117,6 +118,7 @@ def load():
     L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
     L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
     L.sp_kmer_pca_signs.argtypes = [vp, vp, i64, ci, vp, vp, ci, vp, vp]
+    L.sp_hclust_complete.argtypes = [vp, vp, ci, ci, vp, vp]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -850,6 +852,21 @@ class Context:
         rows, vals = np.empty(n_comp, np.int64), np.empty(n_comp, np.float64)
         self._ck(self.L.sp_kmer_pca_signs(self.h, cptr, M, Cn, _p(lengths), _p(U), n_comp, _p(rows), _p(vals)))
         return rows, vals
+
+    def hclust_complete(self, points, want_dist=False):
+        """Complete-linkage clustering of the rows of points (float64 [P, D], all finite) under the Euclidean distance
+        (sp_hclust_complete): returns merges float64 [P - 1, 4] -- (slot x < slot y, height, size) in the order of the
+        nearest-neighbour chain, bit-defined by csrc/sp_hclust.h; heatmap.to_linkage turns them into scipy's linkage --
+        and, with want_dist, the distance matrix float64 [P, P] before the first merge.
+        2 <= P <= HCLUST_MAX_POINTS, D >= 1 (ValueError otherwise, as for a coordinate that is not finite)."""
+        points = np.ascontiguousarray(points, np.float64)
+        if points.ndim != 2:
+            raise ValueError("points must be P x D")
+        P, D = points.shape
+        merges = np.empty((max(P - 1, 0), 4), np.float64)
+        dist = np.empty((P, P), np.float64) if want_dist and P <= HCLUST_MAX_POINTS else None
+        self._ck(self.L.sp_hclust_complete(self.h, _p(points), int(P), int(D), _p(merges), _p(dist)))
+        return (merges, dist) if want_dist else merges
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

@@ -11,7 +11,9 @@ run on the device (bootstrap_engine="device": csrc/sp_kboot.hip).  The k-mer PCA
 (Cluster.pca, Cluster.py:48-75: `.kmer_pca` coordinates and figure) is scikit-learn's
 full-solver PCA restated on the C x C Gram matrix of the Z-scores: the passes over the
 k-mers run on the device from the integer rows (csrc/sp_kpca.hip) or in numpy, the
-eigen-decomposition on the host.  The per-k-mer Student t-test is vectorised over the
+eigen-decomposition on the host.  The clustered heatmap (Cluster.heatmap, Jellyfish.py:524-609) takes its two
+complete-linkage dendrograms from the device (csrc/sp_hclust.hip) or from scipy and draws the figure with matplotlib
+(subphaser_amd/heatmap.py).  The per-k-mer Student t-test is vectorised over the
 M x C matrix instead of looped through a process pool.
 """
 import os
@@ -236,6 +238,113 @@ class Cluster:
         def write():
             if outfig is not None:
                 plot_pca(outfig, scores, percent, chrs, d_sg, labels, colors)
+        if defer:
+            return write
+        write()
+
+    def heatmap(self, kmer_labels, outfig=None, outtsv=None, size=10000, colors=None,
+                heatmap_colors=("green", "black", "red"), defer=False):
+        """The reference's clustered heatmap of the matrix (Jellyfish.py:524-609, drawn there by R's heatmap.2): `size`
+        k-mers sampled without replacement with the seed of the run, each Z-scaled over the chromosomes with the sample
+        variance (the R script's z.scale: ddof = 1, not zscores()), complete-linkage dendrograms under the Euclidean
+        distance over the k-mers (N points x C) and over the chromosomes (C points x N).  k-mers whose variance is 0 or not
+        finite are left out of the pool before sampling (R fails on them; one log line counts them).
+        The two linkages come from Context.hclust_complete (csrc/sp_hclust.hip) when the matrix came with a context that
+        has it and both point counts are within HCLUST_MAX_POINTS, from scipy's pdist + linkage otherwise (one log line
+        says which; heatmap_engine is "device" or "scipy").  Both follow the same procedure, so they agree whenever the
+        distances hold no ties that rounding separates.
+        Chromosomes are ordered as heatmap.2 orders them: reorder() by the chromosome's mean Z over the sample.  The
+        k-mers keep the linkage's own leaf order: every k-mer's mean Z is 0 by construction, so R's reordering of that
+        axis sorts rounding noise, and it is not imitated.
+        Keeps heatmap_rows (the sampled rows of the matrix, ascending), heatmap_z [C, N], heatmap_row_linkage
+        (chromosomes), heatmap_col_linkage (k-mers), heatmap_chrom_order and heatmap_kmer_order.  Fewer than 2 chromosomes
+        or usable k-mers: one log line, heatmap_engine None, nothing written.
+        kmer_labels: output_kmers' KmerLabels (or None): the subgenome a sampled k-mer is significant for, `NA` without.
+        outtsv: `#kmer<TAB>subgenome<TAB>chromosomes in dendrogram order`, then the sampled k-mers in dendrogram order with
+        their Z-scores written with repr.  outfig: dendrograms, side strips of subgenome colours (`colors`, or
+        matplotlib's cycle; white for NA), the image scaled per chromosome row in 100 levels through the 2 or 3
+        heatmap_colors (any other count: ValueError), a colour key; skipped with a warning when matplotlib is missing.
+        defer=True: the figure is not drawn; returns write() that draws it later."""
+        from . import heatmap as hm
+        heatmap_colors = hm.check_colors(heatmap_colors)
+        X = self.raw_data
+        M, C = X.shape
+        self.heatmap_engine = None
+        with np.errstate(all="ignore"):
+            var = X.var(axis=1, ddof=1) if C > 1 else np.zeros(M)
+        good = np.flatnonzero(np.isfinite(var) & (var > 0))
+        logger.info("heatmap: {} of {} k-mers left out of the sample pool (the same frequency on every chromosome, "
+                    "or not finite)".format(M - good.size, M))
+        if C < 2 or good.size < 2:
+            logger.info("heatmap skipped: {} chromosomes, {} usable k-mers (2 of each at least)".format(C, good.size))
+            return None
+        rows = good[hm.sample_rows(good.size, int(size), self.seed)]
+        z = hm.zscale_columns(X[rows])                       # C x N
+        N = len(rows)
+        entry = getattr(getattr(self, "_ctx", None), "hclust_complete", None)
+        if entry is None:
+            why = "no device context with the clustering entry"
+        elif max(N, C) > _native.HCLUST_MAX_POINTS:
+            why = "{} k-mers x {} chromosomes (the device takes up to {} points)".format(N, C, _native.HCLUST_MAX_POINTS)
+        else:
+            why = None
+        if why is None:
+            logger.info("heatmap: complete linkage of {} k-mers and of {} chromosomes on the device".format(N, C))
+            link = lambda pts: hm.to_linkage(entry(pts), len(pts))
+            self.heatmap_engine = "device"
+        else:
+            logger.info("heatmap: {}; using scipy".format(why))
+            from scipy.cluster.hierarchy import linkage
+            from scipy.spatial.distance import pdist
+            link = lambda pts: linkage(pdist(pts), "complete")
+            self.heatmap_engine = "scipy"
+        try:
+            col_Z = link(np.ascontiguousarray(z.T))
+            row_Z = link(z)
+        except BaseException:
+            self.heatmap_engine = None
+            raise
+        chrom_order = hm.reorder(row_Z, z.mean(axis=1))
+        kmer_order = hm.leaves(col_Z)
+        self.heatmap_rows, self.heatmap_z = rows, z
+        self.heatmap_row_linkage, self.heatmap_col_linkage = row_Z, col_Z
+        self.heatmap_chrom_order, self.heatmap_kmer_order = chrom_order, kmer_order
+        # the subgenome every sampled k-mer is significant for: -1 = none
+        sg = np.full(N, -1, np.int64)
+        sg_names = list(getattr(kmer_labels, "sg_names", []))
+        if kmer_labels is not None and len(kmer_labels.keys):
+            lk = np.asarray(kmer_labels.keys)
+            by_key = np.argsort(lk, kind="stable")
+            canon = kmerlib.canonical(self.keys[rows], self.k)
+            at = np.minimum(np.searchsorted(lk[by_key], canon), len(lk) - 1)
+            hit = lk[by_key][at] == canon
+            sg[hit] = np.asarray(kmer_labels.sg_idx)[by_key][at][hit]
+        self.heatmap_kmer_sg = [sg_names[i] if i >= 0 else "NA" for i in sg.tolist()]
+        chrs, kmer_sg = list(self.chrs), self.heatmap_kmer_sg
+        if outtsv is not None:
+            kmers = kmerlib.decode_many(self.keys[rows], self.k)
+            zt = z[chrom_order].T.tolist()                   # N x C, chromosomes in dendrogram order
+            with open(outtsv, "w") as fout:
+                fout.write("\t".join(["#kmer", "subgenome"] + [chrs[i] for i in chrom_order.tolist()]) + "\n")
+                for j in kmer_order.tolist():
+                    fout.write("\t".join([kmers[j], kmer_sg[j]] + [repr(v) for v in zt[j]]) + "\n")
+        all_sg = sorted(set(self.d_sg.values()) | set(sg_names))
+        chrom_sg = [all_sg.index(self.d_sg[c]) for c in chrs]
+        kmer_sgi = [all_sg.index(s) if s != "NA" else -1 for s in kmer_sg]
+
+        def write():
+            if outfig is None:
+                return
+            try:
+                from matplotlib import pyplot as plt
+            except ImportError:
+                logger.warning("matplotlib missing: skipping " + outfig)
+                return
+            pal = colors.split(",") if isinstance(colors, str) else colors
+            if not pal:
+                pal = plt.rcParams["axes.prop_cycle"].by_key()["color"]
+            hm.plot(outfig, z, row_Z, col_Z, chrom_order, kmer_order, chrs, [pal[i % len(pal)] for i in chrom_sg],
+                    [pal[i % len(pal)] if i >= 0 else "white" for i in kmer_sgi], heatmap_colors)
         if defer:
             return write
         write()

@@ -199,6 +199,7 @@ struct sp_ctx {
     sp_buf b_tt;            // k-mer t-test workspace (sp_enrich.hip)
     sp_buf b_kb;            // k-means bootstrap: columns, labels, iteration counts, Gram copies (sp_kboot.hip)
     sp_buf b_kp;            // k-mer PCA: lengths, row statistics, chunk partials, sign candidates (sp_kpca.hip)
+    sp_buf b_hc;            // heatmap clustering: points, the P x P distance matrix, merges, chain state (sp_hclust.hip)
     sp_buf b_wtab, b_enr;   // window table (device) and the enrichment outputs
     sp_buf b_fq;      // global slow queue of the filter
     sp_buf b_fflat;   // flat set tables of the filter (sp_filter.hip)

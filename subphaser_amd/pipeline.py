@@ -78,7 +78,10 @@ CLI = [
         (("-test_method",), dict(choices=list(TEST_METHODS), default="ttest_ind")),
         (("-figfmt",), dict(type=str, choices=["pdf", "png"], default="pdf")),
         (("-heatmap_colors",), dict(nargs="+", metavar="COLOR", default=("green", "black", "red"))),
-        (("-heatmap_options",), dict(metavar="STR", default="")),
+        (("-heatmap_options",), dict(metavar="STR", default="", help="R syntax for heatmap.2 in the reference; the figure "
+                                     "is drawn here without R, so a value is accepted, warned about and ignored")),
+        (("-heatmap_size",), dict(type=int, metavar="INT", default=10000,
+                                  help="k-mers sampled for the clustered heatmap (the reference's constant); 0: no heatmap")),
         (("-just_core",), _FLAG),
     ]),
     ("LTR / Circos", "accepted for command-line compatibility; modules 3-4 stay with the reference",
@@ -363,6 +366,7 @@ class Pipeline:
         t1 = time.perf_counter()
         self._write_in_background(sg_kmers, write, len(kmer_labels.keys) >= _bg_min_rows())
         logger.info("k-mer tests {:.2f} s, text writer started in {:.2f} s".format(t1 - t0, time.perf_counter() - t1))
+        self._heatmap(lay, cl, kmer_labels)      # after output_kmers: it colours the k-mers by their labels (host data only)
         per_sg = np.bincount(kmer_labels.sg_idx, minlength=len(kmer_labels.sg_names))
         logger.info("{} significant subgenome-specific kmers".format(len(kmer_labels.keys)))
         for sg, n in zip(kmer_labels.sg_names, per_sg.tolist()):
@@ -397,6 +401,45 @@ class Pipeline:
                     mk_ckp(lay.ckp(fig))
             except Exception as e:     # the figure is optional
                 logger.warning("k-mer PCA not plotted: {}".format(e))
+        self._background.append((fig, lambda: None, done))
+
+    def _heatmap(self, lay, cl, kmer_labels):
+        """`.kmer.mat.heatmap.tsv` and `.kmer.mat.<figfmt>` (the reference's figure name, __main__.py:461-464).  The table
+        is written here, the figure with the background writers (drawn on the main thread, as the PCA's).  Only a wrong
+        number of -heatmap_colors stops the run, as it stops the reference; any other failure costs these two files."""
+        size = getattr(self, "heatmap_size", 10000)
+        if getattr(self, "heatmap_options", ""):
+            logger.warning("-heatmap_options is R syntax for heatmap.2; the heatmap is drawn without R and ignores `{}`".format(
+                self.heatmap_options))
+        if size is None or size <= 0:
+            logger.info("heatmap skipped: -heatmap_size {}".format(size))
+            return
+        if len(cl.chrs) < 2:
+            logger.info("heatmap skipped: {} chromosome".format(len(cl.chrs)))
+            return
+        from .heatmap import check_colors
+        panel = check_colors(getattr(self, "heatmap_colors", ("green", "black", "red")))      # ValueError: stops the run
+        matfile = lay.out("kmer.mat")
+        tsv, fig = matfile + ".heatmap.tsv", matfile + "." + self.figfmt
+        t0 = time.perf_counter()
+        try:
+            draw = cl.heatmap(kmer_labels, outfig=fig, outtsv=tsv, size=size, colors=getattr(self, "colors", None),
+                              heatmap_colors=panel, defer=True)
+        except Exception as e:
+            logger.warning("heatmap not written: {}".format(e))
+            return
+        if cl.heatmap_engine is None:      # fewer than 2 usable k-mers: logged there
+            return
+        mk_ckp(lay.ckp(tsv))
+        logger.info("heatmap ({}) -> `{}` in {:.2f} s".format(cl.heatmap_engine, os.path.basename(tsv), time.perf_counter() - t0))
+
+        def done():
+            try:
+                draw()
+                if os.path.exists(fig):
+                    mk_ckp(lay.ckp(fig))
+            except Exception as e:     # the figure is optional
+                logger.warning("heatmap not plotted: {}".format(e))
         self._background.append((fig, lambda: None, done))
 
     # ---- stage 4: bin map -> window stack -> enrichment, on the device -----------------------------------
