@@ -29,6 +29,20 @@
 // The three bits inside the word still come from the hashed (k-1)-mer.  k < 5 (cores of fewer than two bases): the old addressing.
 #define MAP_BLOOM_CORE 0x100          // flag in the `nbits` argument of everything below (ctx->bloom_bits carries it)
 #define MAP_BLOOM_NBITS(nb) ((nb) & 0xFF)
+// Runs (profiles/map_runs_notes.md).  Labelled k-mers come in runs -- inside a repeat copy every quad of a lane is a candidate --
+// and a candidate quad goes to the exact table whatever the filter says, so the two-phase walk of k <= 15 (map_unit_scan64)
+// does not ASK the filter inside a run: a lane whose last MAP_RUNS_R probed quads passed on both pairs enqueues the next quad
+// unprobed, both pair flags set, for at most MAP_RUNS_P quads in a row; then it probes again.  The table is exact and the
+// filter only ever said "maybe": a predicted pair that is not labelled finds no tag and sets nothing.  The price is one
+// bucket look-up for a predicted quad that lies just past a run's end.  SP_MAP_RUNS=0 clears the flag (cross-check: the walk
+// then probes every quad).  The k > 15 twin (map_unit_scan64_h) probes every quad: there the rule measured slower.
+#define MAP_RUNS 0x200                // flag in `nbits`, next to MAP_BLOOM_CORE
+#ifndef MAP_RUNS_R
+#define MAP_RUNS_R 2
+#endif
+#ifndef MAP_RUNS_P
+#define MAP_RUNS_P 3
+#endif
 struct map_bloom_probe {
     uint32_t word, bits;
 };

@@ -310,6 +310,11 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
     const int wsh = 32 - (MAP_BLOOM_NBITS(nbits) - 5);
     uint32_t last_wi = 0xFFFFFFFFu, last_w = 0u;                  // the word this lane fetched last (index, content)
     uint32_t h_carry = 0u;                                         // hash of the core the previous quad ended with
+    // runs (sp_map.h), one counter per lane: below MAP_RUNS_R it is the lane's probed quads that passed on both pairs, in a
+    // row; from there on, MAP_RUNS_R + the quads it has predicted since.  Per unit: 0 here, carried over the rounds.
+    static_assert(MAP2_QI == 1, "the runs rule decides a quad from the filter's answer for the quad before it");
+    const bool runs = (nbits & MAP_RUNS) != 0;                     // (uniform)
+    uint32_t run = 0u;
 #pragma unroll 1
     for (int wr = 0; wr < 4; wr += ROUND_W) {
         // ---- phase 1: the filter over ROUND_W words of sixteen starts; the wave's candidate quads go to its queue
@@ -321,7 +326,7 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
                 // MAP2_QI quads per iteration: their filter words are requested together (the word a pair re-uses is known from the
                 // indices alone), then looked at
                 uint32_t bt1[MAP2_QI], bt2[MAP2_QI], wi1[MAP2_QI], wi2[MAP2_QI], f1[MAP2_QI], f2[MAP2_QI];
-                bool v1[MAP2_QI], v2[MAP2_QI], need1[MAP2_QI], need2[MAP2_QI];
+                bool v1[MAP2_QI], v2[MAP2_QI], need1[MAP2_QI], need2[MAP2_QI], guess[MAP2_QI];
                 uint32_t lw = last_wi;
 #pragma unroll
                 for (int q = 0; q < MAP2_QI; q++) {
@@ -355,13 +360,18 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
                     }
                     // a word this lane holds already (the previous pair's) is not fetched again: with the core addressing that
                     // is the case for a third of the pairs -- and a gather is priced per active lane
-                    need1[q] = v1[q] && wi1[q] != lw;
-                    need2[q] = v2[q] && wi2[q] != (v1[q] ? wi1[q] : lw);
+                    // inside a run the quad is not probed at all: it is a candidate on both of its (valid) pairs, and the word the
+                    // lane holds stays the one it fetched last
+                    guess[q] = runs && v1[q] && v2[q] && run - (uint32_t)MAP_RUNS_R < (uint32_t)MAP_RUNS_P;
+                    need1[q] = !guess[q] && v1[q] && wi1[q] != lw;
+                    need2[q] = !guess[q] && v2[q] && wi2[q] != (v1[q] ? wi1[q] : lw);
                     f1[q] = f2[q] = 0;
                     if (need1[q]) f1[q] = bloom[wi1[q]];
                     if (need2[q]) f2[q] = bloom[wi2[q]];
-                    if (v2[q]) lw = wi2[q];
-                    else if (v1[q]) lw = wi1[q];
+                    if (!guess[q]) {
+                        if (v2[q]) lw = wi2[q];
+                        else if (v1[q]) lw = wi1[q];
+                    }
                 }
                 last_wi = lw;
 #pragma unroll
@@ -369,9 +379,13 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
                     const int j = 16 * w + r0 + 4 * q;
                     const uint32_t wd1 = v1[q] ? (need1[q] ? f1[q] : last_w) : 0u;
                     const uint32_t wd2 = v2[q] ? (need2[q] ? f2[q] : (v1[q] ? wd1 : last_w)) : 0u;
-                    if (v2[q]) last_w = wd2;
-                    else if (v1[q]) last_w = wd1;
-                    const bool cand1 = (wd1 & bt1[q]) == bt1[q], cand2 = (wd2 & bt2[q]) == bt2[q];       // (an invalid pair's word is 0: never a candidate)
+                    if (!guess[q]) {
+                        if (v2[q]) last_w = wd2;
+                        else if (v1[q]) last_w = wd1;
+                    }
+                    const bool cand1 = guess[q] || (wd1 & bt1[q]) == bt1[q], cand2 = guess[q] || (wd2 & bt2[q]) == bt2[q];       // (an invalid pair's word is 0: never a candidate)
+                    // (a probed quad that passes keeps a run going: back to MAP_RUNS_R, the next MAP_RUNS_P quads are predicted)
+                    run = guess[q] ? run + 1u : (cand1 && cand2) ? (run < (uint32_t)MAP_RUNS_R ? run + 1u : (uint32_t)MAP_RUNS_R) : 0u;
                     const unsigned long long bal = __ballot(cand1 || cand2);
                     if (cand1 || cand2)
                         queue[qn + __builtin_amdgcn_mbcnt_hi((uint32_t)(bal >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)bal, 0u))] =
@@ -929,7 +943,8 @@ int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n
     // round 6: words addressed by the smaller-hashed core of the (k-1)-mer (sp_map.h); SP_MAP_FILTER=x keeps the round-1
     // addressing by the (k-1)-mer itself (cross-check).  ctx->bloom_bits carries the flag to every kernel that probes.
     const char *env_mf = getenv("SP_MAP_FILTER");
-    const int mode = (env_mf && env_mf[0] == 'x') ? 0 : MAP_BLOOM_CORE;
+    const char *env_runs = getenv("SP_MAP_RUNS");       // SP_MAP_RUNS=0: the k <= 15 walk probes every quad (cross-check of the runs rule, sp_map.h)
+    const int mode = ((env_mf && env_mf[0] == 'x') ? 0 : MAP_BLOOM_CORE) | ((env_runs && env_runs[0] == '0') ? 0 : MAP_RUNS);
     for (;;) {
         const size_t bytes = ((size_t)1 << bits) / 8;
         SP_HIP(ctx, hipMemsetAsync(ctx->d_bloom, 0, bytes, ctx->stream));
