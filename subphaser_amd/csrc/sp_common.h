@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "../../include/subphaser_hip.h"
+#include "sp_carve.h"
 
 #define SP_WAVE 64
 
@@ -48,21 +49,6 @@ struct sp_chrom {
 struct sp_buf {
     void *p = nullptr;
     int64_t cap = 0;
-};
-
-// bump carver: arrays laid out one after the other in a device buffer, each at a 256-byte-aligned offset.  A layout is
-// a function of the carver that makes its take() calls in buffer order: run on sp_carve() it sizes the buffer (`off`),
-// run on sp_carve(buffer) it hands out the pointers.
-struct sp_carve {
-    uintptr_t base;
-    size_t off = 0;
-    explicit sp_carve(void *buffer = nullptr) : base((uintptr_t)buffer) {}
-    template <typename T>
-    T *take(size_t n) {
-        T *p = (T *)(base + off);
-        off += (n * sizeof(T) + 255) & ~(size_t)255;
-        return p;
-    }
 };
 
 // temporary device allocation, released at scope exit (error returns included)
@@ -185,6 +171,24 @@ struct sp_ctx {
     void *h_desc = nullptr;      // page-locked descriptor table of a batched list count issued on the context's own stream
     int64_t h_desc_cap = 0;
     hipEvent_t lane_go = nullptr;
+    // Issues a chain on an auxiliary lane: binds `lane` and `stream` to it (a null lane: the context's own stream, nothing
+    // changes) and puts both back at scope exit -- the error returns of SP_HIP / SP_LAUNCH included.
+    struct lane_scope {
+        sp_ctx *ctx;
+        hipStream_t saved;
+        lane_scope(sp_ctx *c, lane_t *ln) : ctx(c), saved(c->stream) {
+            if (ln) {
+                ctx->lane = ln;
+                ctx->stream = ln->stream;
+            }
+        }
+        lane_scope(const lane_scope &) = delete;
+        lane_scope &operator=(const lane_scope &) = delete;
+        ~lane_scope() {
+            ctx->lane = nullptr;
+            ctx->stream = saved;
+        }
+    };
     // sparse engine (k = 16..32)
     bool sparse_mode = false;
     bool list_mode = false;     // k <= 15, engine 3: per-chromosome sorted (SLOT, count) lists in `sparse`, no byte tables;

@@ -5,6 +5,7 @@
 // (reference: subphaser/Jellyfish.py:671-704).
 #include "sp_device.h"
 #include "sp_c2batch.h"
+#include "sp_c2plan.h"
 #include "sp_internal.h"
 
 // ----------------------------------------------------------------- K1 / engine 1
@@ -376,8 +377,258 @@ int sp_ovf_finalize_split(sp_ctx *ctx, unsigned long long *keys, uint32_t *cnts,
     return SP_OK;
 }
 
+// ----------------------------------------------------------------- lanes (k <= 15 here, k > 15 in sp_sparse2.hip)
+// lanes 0 .. n - 1 get their stream and `done` event, the context its lane_go event, each created once
+int sp_lanes_open(sp_ctx *ctx, int n) {
+    for (int l = 0; l < n; l++)
+        if (!ctx->lanes[l].stream) {
+            SP_HIP(ctx, hipStreamCreateWithFlags(&ctx->lanes[l].stream, hipStreamNonBlocking));
+            SP_HIP(ctx, hipEventCreateWithFlags(&ctx->lanes[l].done, hipEventDisableTiming));
+        }
+    if (n && !ctx->lane_go) SP_HIP(ctx, hipEventCreateWithFlags(&ctx->lane_go, hipEventDisableTiming));
+    return SP_OK;
+}
+// the main stream goes on when every lane is done
+int sp_lanes_join(sp_ctx *ctx, int n) {
+    for (int l = 0; l < n; l++) {
+        SP_HIP(ctx, hipEventRecord(ctx->lanes[l].done, ctx->lanes[l].stream));
+        SP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lanes[l].done, 0));
+    }
+    return SP_OK;
+}
+// after an error: nothing of the lanes' may still run on the shared scratch when the caller returns (ctx->err is kept)
+void sp_lanes_drain(sp_ctx *ctx, int n) {
+    const std::string msg = ctx->err;
+    for (int l = 0; l < n; l++) hipStreamSynchronize(ctx->lanes[l].stream);
+    hipStreamSynchronize(ctx->stream);
+    ctx->err = msg;
+}
+
+// ----------------------------------------------------------------- sp_count at k <= 15
+// what a call settles before its loop over the chromosomes
+struct count_job {
+    sp_kparams kp;
+    int64_t nslots;
+    int lower, engine, first, last;
+    int64_t longest = 0, total_len = 0;     // of the chromosomes [first, last)
+    bool list_mode = false, sized_by_sample = true, batch = false;
+    int n_lanes = 0;
+    unsigned long long *d_len = nullptr;    // per chromosome: sum, n (counts >= lower), overflow pairs, engine 2's region-overrun flag
+    std::vector<char> by_engine2;
+};
+
+// Engine choice by table occupancy.  A chromosome fills at most len / nslots of its dense table; below 1/3 (the
+// Arabidopsis-like 20-Mb chromosomes at k = 15: 4 %, the peanut-like 128-Mb ones: 24 %) clearing, writing and
+// streaming 512 MiB per chromosome through the filter costs more than it saves, so the counts are kept as LISTS of
+// (slot, count >= lower) pairs in ascending slot order instead (engine 3: the same partition chain ending in
+// c2_count_list), joined by the list filter.  Measured per pass: Arabidopsis-like 13.0 -> 6.3 ms, peanut-like
+// 35.8 -> 31.6 ms; a wheat-like chromosome (670 Mb: more k-mers than slots) stays on byte tables.
+// Whole-genome calls on library-owned tables only (the multi-GPU table exchange needs the byte tables).  Above
+// SP_TABLE_MAXC chromosomes the byte-table filter cannot run, so engine 0 keeps lists whatever the occupancy; the list
+// filter takes any number of chromosomes here (sps_filter_passengers above SP_LIST_MAXC).
+static int count_list_mode(sp_ctx *ctx, count_job &J, bool whole) {
+    const char *env3 = getenv("SP_LIST_ENGINE");      // "0": never, "1": whenever possible (tests)
+    bool possible = whole && sp_engine2_supported(J.nslots);      // (a whole-genome call: J.longest is the genome's)
+    for (auto &c : ctx->chroms) possible = possible && !c.tab_external;
+    if (J.engine == 3) {
+        if (!possible)
+            return sp_fail(ctx, SP_EUNSUP, "count engine 3 (lists) needs k with 2^17..2^31 dense slots, a whole-genome call "
+                                           "and library-owned tables");
+        J.list_mode = true;
+    } else if (J.engine == 0 && possible && ctx->chroms.size() > SP_TABLE_MAXC) {
+        J.list_mode = true;
+    } else if (J.engine == 0 && possible && ctx->chroms.size() <= 64) {     // (the automatic choice: sps_join_blk's lists)
+        J.list_mode = (env3 && env3[0] == '1') || (!(env3 && env3[0] == '0') && J.longest > 0 && J.longest * 3 < J.nslots);
+    }
+    return SP_OK;
+}
+
+// How many auxiliary streams the chains run on (J.n_lanes), and the streams themselves.
+// Small genomes (engine 3): chromosomes are counted on up to three more streams side by side (SP_LANES=0: one stream).
+// Byte tables (engine 2, whole-genome calls): the chains run on SP_LANES_DENSE + 1 auxiliary streams (default 4)
+// and NOT on the context's stream.  A chromosome's chain has five single-workgroup kernels (sample histogram,
+// offsets, tile starts, overflow scan / place: ~0.15 ms of a 3-ms chain during which the chip idles) and its big
+// kernels are bound by different things; side by side they fill each other's gaps (130.5 -> 120.5 ms per
+// wheat-like pass).  A lane waits for ITS chromosome's pack kernel only (sp_chrom::ev_packed), so counting starts
+// while the context's stream is still packing the chromosomes behind it.
+static int count_open_lanes(sp_ctx *ctx, count_job &J, bool dense_lanes) {
+    const char *el = getenv(J.list_mode ? "SP_LANES" : "SP_LANES_DENSE");
+    // (batched list counts: two groups since round 6 -- with c2_count_list16's two workgroups per CU a launch fills the chip
+    // better, and Arabidopsis-like passes take 4.10 / 4.13 / 4.24 / 4.42 / 4.45 ms with 1 / 2 / 3 / 5 / 7 extra streams)
+    int n_lanes = el ? atoi(el) : (J.batch ? 1 : 3);
+    // (toy inputs: chains that last microseconds gain nothing from side-by-side streams and pay for their events
+    // and joins -- 105 against 41 ms per iteration of the fuzzer; the streams are for genomes)
+    if (!el && J.total_len < (1LL << 24)) n_lanes = 0;
+    if (dense_lanes && n_lanes > 0) n_lanes++;       // (the context's stream takes no chain)
+    if (n_lanes > SP_MAX_LANES) n_lanes = SP_MAX_LANES;
+    if (n_lanes < 0) n_lanes = 0;
+    // every lane owns a workspace of ~6 bytes per base of the longest chromosome (sp_count2.hip / sp_sparse2.hip):
+    // lanes whose workspace is not allocated yet must fit what the device has free, with a margin (advisor r04)
+    // (a batched list count puts a whole GROUP of chromosomes into one lane's workspace: about 1 / (lanes + 1) of the
+    // genome, at most one chromosome more -- advisor r05)
+    const int64_t per_lane = 6 * (J.batch ? J.total_len / (int64_t)(n_lanes + 1) + J.longest : J.longest) + (256LL << 20);
+    size_t free_b = 0, total_b = 0;
+    if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
+        int64_t need[SP_MAX_LANES];
+        for (int l = 0; l < n_lanes; l++) need[l] = ctx->lanes[l].ws2_bytes >= per_lane ? 0 : per_lane;
+        const int fit = sp_lanes_fit(need, n_lanes, (int64_t)free_b, (int64_t)total_b);
+        if (fit < n_lanes) {
+            if (getenv("SP_DEBUG_COUNT")) fprintf(stderr, "[sp] count: %d of %d lanes fit the free device memory\n", fit, n_lanes);
+            n_lanes = (dense_lanes && fit == 1) ? 0 : fit;      // (one dense lane = the plain single-stream path)
+        }
+    }
+    const int rc = sp_lanes_open(ctx, n_lanes);
+    if (rc) return rc;
+    if (n_lanes && J.list_mode) {      // the lanes start after what is queued on the main stream (packing)
+        SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
+        for (int l = 0; l < n_lanes; l++) SP_HIP(ctx, hipStreamWaitEvent(ctx->lanes[l].stream, ctx->lane_go, 0));
+    }
+    J.n_lanes = n_lanes;
+    return SP_OK;
+}
+
+// a chromosome's list holds `need` pairs at least
+static int list_reserve(sp_ctx *ctx, sp_sparse_chrom &o, int64_t need) {
+    if (need <= o.cap) return SP_OK;
+    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    if (o.d_keys) hipFree(o.d_keys);
+    if (o.d_cnts) hipFree(o.d_cnts);
+    o = sp_sparse_chrom();
+    SP_HIP(ctx, hipMalloc(&o.d_keys, (size_t)(need + 1) * 8));
+    SP_HIP(ctx, hipMalloc(&o.d_cnts, (size_t)(need + 1) * 4));
+    o.cap = need;
+    return SP_OK;
+}
+// list mode: chromosome ci's list is emptied and sized
+static int list_begin(sp_ctx *ctx, const count_job &J, size_t ci) {
+    sp_sparse_chrom &o = ctx->sparse[ci];
+    o.n = 0;
+    o.length_sum = 0;
+    // every kept slot accounts for >= lower k-mer occurrences (and there are at most nslots of them)
+    int64_t need = ctx->chroms[ci].len / J.lower + 16;
+    if (need > J.nslots) need = J.nslots;
+    return list_reserve(ctx, o, need);
+}
+
+// List mode, batched (round 5): ONE launch per kernel type (sp_c2batch.h) for a group of chromosomes instead of a chain
+// of ten launches per chromosome on four streams.
+static int count_batch(sp_ctx *ctx, count_job &J) {
+    for (size_t ci = (size_t)J.first; ci < (size_t)J.last; ci++) {
+        if (!ctx->chroms[ci].d_pk && ctx->chroms[ci].len > 0) return sp_fail(ctx, SP_EINVAL, "chromosome %zu not loaded", ci);
+        const int rc = list_begin(ctx, J, ci);
+        if (rc) return rc;
+        J.by_engine2[ci] = 1;
+    }
+    SP_HIP(ctx, hipMemsetAsync(J.d_len + 4 * (size_t)J.first, 0, 4 * (size_t)(J.last - J.first) * sizeof(unsigned long long), ctx->stream));
+    // groups of chromosomes (g, g + G, g + 2 G, ...) on the context's stream and the lanes: one launch per kernel
+    // type and GROUP -- the kernels of a chain are bound by different things and fill each other's gaps side by
+    // side (one group: 15.4 ms per peanut-like pass against 13.9 for per-chromosome chains on four streams)
+    const int G = J.n_lanes + 1;
+    if (J.n_lanes) {       // (the lanes were told to wait for lane_go when they were opened; it must follow the memset)
+        SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
+        for (int l = 0; l < J.n_lanes; l++) SP_HIP(ctx, hipStreamWaitEvent(ctx->lanes[l].stream, ctx->lane_go, 0));
+    }
+    for (int g = 0; g < G; g++) {
+        std::vector<int> idx;
+        for (int ci = J.first + g; ci < J.last; ci += G) idx.push_back(ci);
+        if (idx.empty()) continue;
+        sp_ctx::lane_scope on(ctx, g ? &ctx->lanes[g - 1] : nullptr);
+        const int rc = sp_count_engine3_batch(ctx, idx.data(), (int)idx.size(), J.kp, J.lower, J.d_len);
+        if (rc) return rc;
+    }
+    return SP_OK;
+}
+
+// chromosome ci's partition chain (sp_count2.hip) on lane ln, or on the context's stream
+static int count_chrom_chain(sp_ctx *ctx, count_job &J, size_t ci, sp_ctx::lane_t *ln) {
+    SP_HIP(ctx, hipMemsetAsync(J.d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ln ? ln->stream : ctx->stream));
+    sp_ctx::lane_scope on(ctx, ln);
+    const int rc = sp_count_engine2(ctx, ctx->chroms[ci], J.kp, J.lower, J.d_len + 4 * ci, !J.sized_by_sample,
+                                    J.list_mode ? &ctx->sparse[ci] : nullptr);
+    if (!rc) J.by_engine2[ci] = 1;
+    return rc;
+}
+
+// list mode, one chain per chromosome: chromosome ci on stream ci % (1 + lanes in use); lane 0 is the context's own stream
+static int count_chrom_list(sp_ctx *ctx, count_job &J, size_t ci) {
+    const int rc = list_begin(ctx, J, ci);
+    if (rc) return rc;
+    const size_t G = (size_t)(J.n_lanes + 1);
+    return count_chrom_chain(ctx, J, ci, (J.n_lanes > 0 && ci % G) ? &ctx->lanes[ci % G - 1] : nullptr);
+}
+
+// byte table by engine 2 (the auxiliary streams only; each waits for its chromosome's pack kernel)
+static int count_chrom_table(sp_ctx *ctx, count_job &J, size_t ci) {
+    sp_chrom &c = ctx->chroms[ci];
+    sp_ctx::lane_t *ln = J.n_lanes > 0 ? &ctx->lanes[ci % (size_t)J.n_lanes] : nullptr;
+    if (ln && c.ev_packed) SP_HIP(ctx, hipStreamWaitEvent(ln->stream, c.ev_packed, 0));
+    // (round 6 audit: the one reader of the byte tables that returns without a host synchronisation is k3_emit
+    // behind sp_filter_fetch_async; copy_event sits right behind it on the context's stream -- a count that
+    // follows without sp_filter_fetch_wait must not rewrite the tables under it)
+    if (ln && ctx->copy_event) SP_HIP(ctx, hipStreamWaitEvent(ln->stream, ctx->copy_event, 0));
+    return count_chrom_chain(ctx, J, ci, ln);
+}
+
+// byte table by engine 1: global atomics into a u32 scratch table, then one pass to the byte table
+static int count_chrom_atomic(sp_ctx *ctx, const count_job &J, size_t ci, int64_t need_ovf) {
+    sp_chrom &c = ctx->chroms[ci];
+    const int64_t nslots = J.nslots;
+    SP_HIP(ctx, hipMemsetAsync(J.d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    const int64_t n_buckets = (nslots + (1LL << SP_OVF_SHIFT) - 1) >> SP_OVF_SHIFT;
+    int rc = sp_buf_ensure(ctx, ctx->b_tab32, nslots * 4);
+    if (rc) return rc;
+    rc = sp_buf_ensure(ctx, ctx->b_ovfw, need_ovf * 8 + (3 * n_buckets + 1) * 4 + 256);
+    if (rc) return rc;
+    uint32_t *tab32 = (uint32_t *)ctx->b_tab32.p;
+    uint2 *ovf_tmp = (uint2 *)ctx->b_ovfw.p;
+    uint32_t *seg_base = (uint32_t *)(ovf_tmp + need_ovf), *seg_cnt = seg_base + n_buckets, *seg_off = seg_cnt + n_buckets;
+    SP_HIP(ctx, hipMemsetAsync(tab32, 0, (size_t)nslots * sizeof(uint32_t), ctx->stream));
+    int64_t n_units = (c.len + SP_UNIT - 1) / SP_UNIT;
+    if (n_units > 0) {
+        int grid = grid_for(ctx, n_units, 256, 16);
+        SP_LAUNCH(ctx, "k1_count_atomic", k1_count_atomic, dim3(grid), dim3(256), 0, c.d_pk, c.d_nm,
+                  n_units, sp_make_kparams32(J.kp.k), tab32);
+    }
+    int grid2 = (int)(n_buckets < (int64_t)ctx->n_cu * 8 ? n_buckets : (int64_t)ctx->n_cu * 8);
+    SP_LAUNCH(ctx, "k1_narrow", k1_narrow, dim3(grid2), dim3(256), 0, (const uint32_t *)tab32, nslots,
+              (uint32_t)J.lower, c.d_tab, J.d_len + 4 * ci, ovf_tmp, (unsigned long long)need_ovf, seg_base, seg_cnt,
+              n_buckets);
+    return sp_ovf_finalize(ctx, c, ovf_tmp, seg_base, seg_cnt, seg_off, n_buckets, nullptr);   // (k1_narrow keeps an exact cursor in d_len[2])
+}
+
+// every chromosome of [first, last) issued on its stream (an error return leaves the lanes to the caller's drain)
+static int count_all(sp_ctx *ctx, count_job &J) {
+    if (J.batch) return count_batch(ctx, J);
+    for (size_t ci = (size_t)J.first; ci < (size_t)J.last; ci++) {
+        sp_chrom &c = ctx->chroms[ci];
+        if (!c.d_pk && c.len > 0) return sp_fail(ctx, SP_EINVAL, "chromosome %zu not loaded", ci);
+        int rc;
+        if (J.list_mode) {
+            rc = count_chrom_list(ctx, J, ci);
+        } else {
+            if (!c.d_tab) SP_HIP(ctx, hipMalloc(&c.d_tab, (size_t)J.nslots));
+            const int64_t need_ovf = c.len / 255 + 16;      // every overflow pair accounts for >= 255 k-mer occurrences
+            if (need_ovf > c.cap_ovf) {
+                if (c.d_ovf) {
+                    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+                    hipFree(c.d_ovf);
+                    c.d_ovf = nullptr;
+                }
+                SP_HIP(ctx, hipMalloc(&c.d_ovf, (size_t)need_ovf * sizeof(uint2)));
+                c.cap_ovf = need_ovf;
+            }
+            int eng = J.engine;
+            if (eng == 0) eng = (sp_engine2_supported(J.nslots) && c.len >= (1 << 22)) ? 2 : 1;
+            rc = eng == 2 ? count_chrom_table(ctx, J, ci) : count_chrom_atomic(ctx, J, ci, need_ovf);
+        }
+        if (rc) return rc;
+    }
+    return SP_OK;
+}
+
 extern "C" {
 
+// validate, choose the engine, set up the lanes, issue every chromosome, join, read the tallies back, recount overruns
 static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first, int last) {
     if (!ctx) return SP_EINVAL;
     if (k < 1 || k > 32) return sp_fail(ctx, SP_EUNSUP, "k=%d unsupported (1..32)", k);
@@ -409,40 +660,17 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
         return SP_OK;
     }
     ctx->sparse_mode = false;
-    const sp_kparams kp = sp_make_kparams(k);
-    const int64_t nslots = sp_dense_slots(k);
-    // Engine choice by table occupancy.  A chromosome fills at most len / nslots of its dense table; below 1/3 (the
-    // Arabidopsis-like 20-Mb chromosomes at k = 15: 4 %, the peanut-like 128-Mb ones: 24 %) clearing, writing and
-    // streaming 512 MiB per chromosome through the filter costs more than it saves, so the counts are kept as LISTS of
-    // (slot, count >= lower) pairs in ascending slot order instead (engine 3: the same partition chain ending in
-    // c2_count_list), joined by the list filter.  Measured per pass: Arabidopsis-like 13.0 -> 6.3 ms, peanut-like
-    // 35.8 -> 31.6 ms; a wheat-like chromosome (670 Mb: more k-mers than slots) stays on byte tables.
-    // Whole-genome calls on library-owned tables only (the multi-GPU table exchange needs the byte tables).  Above
-    // SP_TABLE_MAXC chromosomes the byte-table filter cannot run, so engine 0 keeps lists whatever the occupancy; the list
-    // filter takes any number of chromosomes here (sps_filter_passengers above SP_LIST_MAXC).
-    bool list_mode = false;
-    {
-        const char *env3 = getenv("SP_LIST_ENGINE");      // "0": never, "1": whenever possible (tests)
-        bool whole = first == 0 && last == (int)ctx->chroms.size();
-        bool possible = whole && sp_engine2_supported(nslots);
-        bool external = false;
-        int64_t longest = 0;
-        for (auto &c : ctx->chroms) {
-            external = external || c.tab_external;
-            longest = c.len > longest ? c.len : longest;
-        }
-        possible = possible && !external;
-        if (engine == 3) {
-            if (!possible)
-                return sp_fail(ctx, SP_EUNSUP, "count engine 3 (lists) needs k with 2^17..2^31 dense slots, a whole-genome call "
-                                               "and library-owned tables");
-            list_mode = true;
-        } else if (engine == 0 && possible && ctx->chroms.size() > SP_TABLE_MAXC) {
-            list_mode = true;
-        } else if (engine == 0 && possible && ctx->chroms.size() <= 64) {     // (the automatic choice: sps_join_blk's lists)
-            list_mode = (env3 && env3[0] == '1') || (!(env3 && env3[0] == '0') && longest > 0 && longest * 3 < nslots);
-        }
+    const size_t C = ctx->chroms.size();
+    const bool whole = first == 0 && last == (int)C;
+    count_job J{sp_make_kparams(k), sp_dense_slots(k), lower_count, engine, first, last};
+    for (size_t ci = (size_t)first; ci < (size_t)last; ci++) {
+        J.longest = ctx->chroms[ci].len > J.longest ? ctx->chroms[ci].len : J.longest;
+        J.total_len += ctx->chroms[ci].len;
     }
+    const int64_t nslots = J.nslots;
+    int rc = count_list_mode(ctx, J, whole);
+    if (rc) return rc;
+    const bool list_mode = J.list_mode;
     // a new k invalidates old tables
     if (ctx->k != k || ctx->nslots != nslots) {
         SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
@@ -463,244 +691,35 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     ctx->counted = false;
     ctx->filtered = false;
     ctx->list_mode = list_mode;
-    const size_t C = ctx->chroms.size();
     if (list_mode && ctx->sparse.size() != C) {
         sp_sparse_release(ctx);
         ctx->sparse.assign(C, sp_sparse_chrom());
     }
-    // per chromosome: sum, n (counts >= lower), overflow pairs, engine 2's region-overrun flag (a buffer of its own: the
-    // lanes below clear their entries on their own streams, next to whatever the main stream still runs)
-    int rc = sp_buf_ensure(ctx, ctx->b_cntlen, (int64_t)(4 * C * sizeof(unsigned long long)));
+    // (a buffer of its own: the lanes clear their entries on their own streams, next to whatever the main stream still runs)
+    rc = sp_buf_ensure(ctx, ctx->b_cntlen, (int64_t)(4 * C * sizeof(unsigned long long)));
     if (rc) return rc;
-    unsigned long long *d_len = (unsigned long long *)ctx->b_cntlen.p;
+    unsigned long long *d_len = J.d_len = (unsigned long long *)ctx->b_cntlen.p;
     const char *env_exact = getenv("SP_C2_EXACT");      // "1": size the buckets from the full histogram (round-2 path)
-    const bool sized_by_sample = !(env_exact && env_exact[0] == '1');
-    std::vector<char> by_engine2(C, 0);
-    // small genomes (engine 3): count chromosomes on up to three more streams side by side (SP_LANES=0: one stream)
-    // Byte tables (engine 2, whole-genome calls): the chains run on SP_LANES_DENSE + 1 auxiliary streams (default 4)
-    // and NOT on the context's stream.  A chromosome's chain has five single-workgroup kernels (sample histogram,
-    // offsets, tile starts, overflow scan / place: ~0.15 ms of a 3-ms chain during which the chip idles) and its big
-    // kernels are bound by different things; side by side they fill each other's gaps (130.5 -> 120.5 ms per
-    // wheat-like pass).  A lane waits for ITS chromosome's pack kernel only (sp_chrom::ev_packed), so counting starts
-    // while the context's stream is still packing the chromosomes behind it.
-    int n_lanes = 0;
-    const bool dense_lanes = !list_mode && C > 1 && first == 0 && last == (int)C && engine != 1;
-    // round 5: list mode counts all its chromosomes with ONE launch per kernel type (sp_c2batch.h) instead of a chain
-    // of ten launches per chromosome on four streams; SP_C2_BATCH=0 keeps the lanes (cross-check)
-    const char *env_batch = getenv("SP_C2_BATCH");
+    const bool sized_by_sample = J.sized_by_sample = !(env_exact && env_exact[0] == '1');
+    J.by_engine2.assign(C, 0);
+    // list mode batches its chromosomes (count_batch); SP_C2_BATCH=0 keeps the per-chromosome chains on the lanes (cross-check)
     // (chromosomes below 2^26 bases: at 128 Mb -- peanut-like -- the per-chromosome chains on four streams are 3 % ahead;
     // SP_C2_BATCH=1 batches whatever the lengths)
-    int64_t longest = 0;
-    for (size_t ci = (size_t)first; ci < (size_t)last; ci++) longest = ctx->chroms[ci].len > longest ? ctx->chroms[ci].len : longest;
-    const bool batch = list_mode && last - first > 1 && sized_by_sample && !(env_batch && env_batch[0] == '0') &&
-                       (longest < (1LL << 26) || (env_batch && env_batch[0] == '1'));
+    const char *env_batch = getenv("SP_C2_BATCH");
+    J.batch = list_mode && last - first > 1 && sized_by_sample && !(env_batch && env_batch[0] == '0') &&
+              (J.longest < (1LL << 26) || (env_batch && env_batch[0] == '1'));
+    const bool dense_lanes = !list_mode && C > 1 && whole && engine != 1;
     if ((list_mode && C > 1) || dense_lanes) {
-        const char *el = getenv(list_mode ? "SP_LANES" : "SP_LANES_DENSE");
-        // (batched list counts: two groups since round 6 -- with c2_count_list16's two workgroups per CU a launch fills the chip
-        // better, and Arabidopsis-like passes take 4.10 / 4.13 / 4.24 / 4.42 / 4.45 ms with 1 / 2 / 3 / 5 / 7 extra streams)
-        n_lanes = el ? atoi(el) : (batch ? 1 : 3);
-        // (toy inputs: chains that last microseconds gain nothing from side-by-side streams and pay for their events
-        // and joins -- 105 against 41 ms per iteration of the fuzzer; the streams are for genomes)
-        int64_t total_len = 0;
-        for (size_t ci = (size_t)first; ci < (size_t)last; ci++) total_len += ctx->chroms[ci].len;
-        if (!el && total_len < (1LL << 24)) n_lanes = 0;
-        if (dense_lanes && n_lanes > 0) n_lanes++;       // (the context's stream takes no chain)
-        if (n_lanes > SP_MAX_LANES) n_lanes = SP_MAX_LANES;
-        if (n_lanes < 0) n_lanes = 0;
-        {   // every lane owns a workspace of ~6 bytes per base of the longest chromosome (sp_count2.hip / sp_sparse2.hip):
-            // lanes whose workspace is not allocated yet must fit what the device has free, with a margin (advisor r04)
-            int64_t longest_c = 0;
-            for (size_t ci = (size_t)first; ci < (size_t)last; ci++) longest_c = ctx->chroms[ci].len > longest_c ? ctx->chroms[ci].len : longest_c;
-            // (a batched list count puts a whole GROUP of chromosomes into one lane's workspace: about 1 / (lanes + 1) of the
-            // genome, at most one chromosome more -- advisor r05)
-            const int64_t per_lane = 6 * (batch ? total_len / (int64_t)(n_lanes + 1) + longest_c : longest_c) + (256LL << 20);
-            size_t free_b = 0, total_b = 0;
-            if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-                int64_t budget = (int64_t)free_b - (int64_t)(total_b / 16);      // keep a sixteenth of the device free
-                int fit = 0;
-                for (int l = 0; l < n_lanes; l++) {
-                    const int64_t need = ctx->lanes[l].ws2_bytes >= per_lane ? 0 : per_lane;
-                    if (need > budget) break;
-                    budget -= need;
-                    fit++;
-                }
-                if (fit < n_lanes) {
-                    if (getenv("SP_DEBUG_COUNT")) fprintf(stderr, "[sp] count: %d of %d lanes fit the free device memory\n", fit, n_lanes);
-                    n_lanes = (dense_lanes && fit == 1) ? 0 : fit;      // (one dense lane = the plain single-stream path)
-                }
-            }
-        }
-        for (int l = 0; l < n_lanes; l++) {
-            if (!ctx->lanes[l].stream) {
-                SP_HIP(ctx, hipStreamCreateWithFlags(&ctx->lanes[l].stream, hipStreamNonBlocking));
-                SP_HIP(ctx, hipEventCreateWithFlags(&ctx->lanes[l].done, hipEventDisableTiming));
-            }
-        }
-        if (n_lanes && !ctx->lane_go) SP_HIP(ctx, hipEventCreateWithFlags(&ctx->lane_go, hipEventDisableTiming));
-        if (n_lanes && list_mode) {      // the lanes start after what is queued on the main stream (packing)
-            SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
-            for (int l = 0; l < n_lanes; l++) SP_HIP(ctx, hipStreamWaitEvent(ctx->lanes[l].stream, ctx->lane_go, 0));
-        }
+        rc = count_open_lanes(ctx, J, dense_lanes);
+        if (rc) return rc;
     }
-    // (a lambda: an error return inside must not leave the other lanes' kernels running on the shared scratch)
-    auto count_all = [&]() -> int {
-        if (batch) {
-            for (size_t ci = (size_t)first; ci < (size_t)last; ci++) {
-                sp_chrom &c = ctx->chroms[ci];
-                if (!c.d_pk && c.len > 0) return sp_fail(ctx, SP_EINVAL, "chromosome %zu not loaded", ci);
-                sp_sparse_chrom &o = ctx->sparse[ci];
-                o.n = 0;
-                o.length_sum = 0;
-                int64_t need = c.len / lower_count + 16;     // (as below: every kept slot accounts for >= lower occurrences)
-                if (need > nslots) need = nslots;
-                if (need > o.cap) {
-                    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    if (o.d_keys) hipFree(o.d_keys);
-                    if (o.d_cnts) hipFree(o.d_cnts);
-                    o.d_keys = nullptr;
-                    o.d_cnts = nullptr;
-                    o.cap = 0;
-                    SP_HIP(ctx, hipMalloc(&o.d_keys, (size_t)(need + 1) * 8));
-                    SP_HIP(ctx, hipMalloc(&o.d_cnts, (size_t)(need + 1) * 4));
-                    o.cap = need;
-                }
-                by_engine2[ci] = 1;
-            }
-            SP_HIP(ctx, hipMemsetAsync(d_len + 4 * (size_t)first, 0, 4 * (size_t)(last - first) * sizeof(unsigned long long), ctx->stream));
-            // groups of chromosomes (g, g + G, g + 2 G, ...) on the context's stream and the lanes: one launch per kernel
-            // type and GROUP -- the kernels of a chain are bound by different things and fill each other's gaps side by
-            // side (one group: 15.4 ms per peanut-like pass against 13.9 for per-chromosome chains on four streams)
-            const int G = n_lanes + 1;
-            if (n_lanes) {       // (the lanes were told to wait for lane_go above; it must follow the memset)
-                SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
-                for (int l = 0; l < n_lanes; l++) SP_HIP(ctx, hipStreamWaitEvent(ctx->lanes[l].stream, ctx->lane_go, 0));
-            }
-            hipStream_t main_stream = ctx->stream;
-            int rcb = SP_OK;
-            for (int g = 0; g < G && !rcb; g++) {
-                std::vector<int> idx;
-                for (int ci = first + g; ci < last; ci += G) idx.push_back(ci);
-                if (idx.empty()) continue;
-                sp_ctx::lane_t *ln = g ? &ctx->lanes[g - 1] : nullptr;
-                if (ln) {
-                    ctx->lane = ln;
-                    ctx->stream = ln->stream;
-                }
-                rcb = sp_count_engine3_batch(ctx, idx.data(), (int)idx.size(), kp, lower_count, d_len);
-                ctx->lane = nullptr;
-                ctx->stream = main_stream;
-            }
-            return rcb;
-        }
-        for (size_t ci = (size_t)first; ci < (size_t)last; ci++) {
-            sp_chrom &c = ctx->chroms[ci];
-            if (!c.d_pk && c.len > 0) return sp_fail(ctx, SP_EINVAL, "chromosome %zu not loaded", ci);
-            if (list_mode) {
-                sp_sparse_chrom &o = ctx->sparse[ci];
-                o.n = 0;
-                o.length_sum = 0;
-                // every kept slot accounts for >= lower k-mer occurrences (and there are at most nslots of them)
-                int64_t need = c.len / lower_count + 16;
-                if (need > nslots) need = nslots;
-                if (need > o.cap) {
-                    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    if (o.d_keys) hipFree(o.d_keys);
-                    if (o.d_cnts) hipFree(o.d_cnts);
-                    o.d_keys = nullptr;
-                    o.d_cnts = nullptr;
-                    o.cap = 0;
-                    SP_HIP(ctx, hipMalloc(&o.d_keys, (size_t)(need + 1) * 8));
-                    SP_HIP(ctx, hipMalloc(&o.d_cnts, (size_t)(need + 1) * 4));
-                    o.cap = need;
-                }
-                // lanes: chromosome ci on stream ci % (1 + lanes in use); lane 0 is the context's own stream
-                sp_ctx::lane_t *ln = (n_lanes > 0 && ci % (size_t)(n_lanes + 1)) ? &ctx->lanes[ci % (size_t)(n_lanes + 1) - 1] : nullptr;
-                hipStream_t main_stream = ctx->stream;
-                SP_HIP(ctx, hipMemsetAsync(d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ln ? ln->stream : main_stream));
-                if (ln) {       // (no early return between here and the restore below)
-                    ctx->lane = ln;
-                    ctx->stream = ln->stream;
-                }
-                rc = sp_count_engine2(ctx, c, kp, lower_count, d_len + 4 * ci, !sized_by_sample, &o);
-                ctx->lane = nullptr;
-                ctx->stream = main_stream;
-                if (rc) return rc;
-                by_engine2[ci] = 1;
-                continue;
-            }
-            if (!c.d_tab) SP_HIP(ctx, hipMalloc(&c.d_tab, (size_t)nslots));
-            // every overflow pair accounts for >= 255 k-mer occurrences
-            const int64_t need_ovf = c.len / 255 + 16;
-            if (need_ovf > c.cap_ovf) {
-                if (c.d_ovf) {
-                    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-                    hipFree(c.d_ovf);
-                    c.d_ovf = nullptr;
-                }
-                SP_HIP(ctx, hipMalloc(&c.d_ovf, (size_t)need_ovf * sizeof(uint2)));
-                c.cap_ovf = need_ovf;
-            }
-            int eng = engine;
-            if (eng == 0) eng = (sp_engine2_supported(nslots) && c.len >= (1 << 22)) ? 2 : 1;
-            if (eng == 2) {
-                // (byte tables: the auxiliary streams only; each waits for its chromosome's pack kernel)
-                sp_ctx::lane_t *ln = n_lanes > 0 ? &ctx->lanes[ci % (size_t)n_lanes] : nullptr;
-                hipStream_t main_stream = ctx->stream;
-                if (ln && c.ev_packed) SP_HIP(ctx, hipStreamWaitEvent(ln->stream, c.ev_packed, 0));
-                // (round 6 audit: the one reader of the byte tables that returns without a host synchronisation is k3_emit
-                // behind sp_filter_fetch_async; copy_event sits right behind it on the context's stream -- a count that
-                // follows without sp_filter_fetch_wait must not rewrite the tables under it)
-                if (ln && ctx->copy_event) SP_HIP(ctx, hipStreamWaitEvent(ln->stream, ctx->copy_event, 0));
-                SP_HIP(ctx, hipMemsetAsync(d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ln ? ln->stream : main_stream));
-                if (ln) {       // (no early return between here and the restore below)
-                    ctx->lane = ln;
-                    ctx->stream = ln->stream;
-                }
-                rc = sp_count_engine2(ctx, c, kp, lower_count, d_len + 4 * ci, !sized_by_sample, nullptr);
-                ctx->lane = nullptr;
-                ctx->stream = main_stream;
-                if (rc) return rc;
-                by_engine2[ci] = 1;
-                continue;
-            }
-            // engine 1: global atomics into a u32 scratch table, then one pass to the byte table
-            SP_HIP(ctx, hipMemsetAsync(d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ctx->stream));
-            const int64_t n_buckets = (nslots + (1LL << SP_OVF_SHIFT) - 1) >> SP_OVF_SHIFT;
-            rc = sp_buf_ensure(ctx, ctx->b_tab32, nslots * 4);
-            if (rc) return rc;
-            rc = sp_buf_ensure(ctx, ctx->b_ovfw, need_ovf * 8 + (3 * n_buckets + 1) * 4 + 256);
-            if (rc) return rc;
-            uint32_t *tab32 = (uint32_t *)ctx->b_tab32.p;
-            uint2 *ovf_tmp = (uint2 *)ctx->b_ovfw.p;
-            uint32_t *seg_base = (uint32_t *)(ovf_tmp + need_ovf), *seg_cnt = seg_base + n_buckets, *seg_off = seg_cnt + n_buckets;
-            SP_HIP(ctx, hipMemsetAsync(tab32, 0, (size_t)nslots * sizeof(uint32_t), ctx->stream));
-            int64_t n_units = (c.len + SP_UNIT - 1) / SP_UNIT;
-            if (n_units > 0) {
-                int grid = grid_for(ctx, n_units, 256, 16);
-                SP_LAUNCH(ctx, "k1_count_atomic", k1_count_atomic, dim3(grid), dim3(256), 0, c.d_pk, c.d_nm,
-                          n_units, sp_make_kparams32(k), tab32);
-            }
-            int grid2 = (int)(n_buckets < (int64_t)ctx->n_cu * 8 ? n_buckets : (int64_t)ctx->n_cu * 8);
-            SP_LAUNCH(ctx, "k1_narrow", k1_narrow, dim3(grid2), dim3(256), 0, (const uint32_t *)tab32, nslots,
-                      (uint32_t)lower_count, c.d_tab, d_len + 4 * ci, ovf_tmp, (unsigned long long)need_ovf, seg_base, seg_cnt,
-                      n_buckets);
-            rc = sp_ovf_finalize(ctx, c, ovf_tmp, seg_base, seg_cnt, seg_off, n_buckets, nullptr);   // (k1_narrow keeps an exact cursor in d_len[2])
-            if (rc) return rc;
-        }
-        return SP_OK;
-    };
-    rc = count_all();
+    rc = count_all(ctx, J);
     if (rc) {
-        const std::string msg = ctx->err;
-        for (int l = 0; l < n_lanes; l++) hipStreamSynchronize(ctx->lanes[l].stream);
-        hipStreamSynchronize(ctx->stream);
-        ctx->err = msg;
+        sp_lanes_drain(ctx, J.n_lanes);
         return rc;
     }
-    for (int l = 0; l < n_lanes; l++) {      // the main stream goes on when every lane is done
-        SP_HIP(ctx, hipEventRecord(ctx->lanes[l].done, ctx->lanes[l].stream));
-        SP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lanes[l].done, 0));
-    }
+    rc = sp_lanes_join(ctx, J.n_lanes);
+    if (rc) return rc;
     std::vector<unsigned long long> h(4 * C);
     SP_HIP(ctx, hipMemcpyAsync(h.data(), d_len, 4 * C * sizeof(unsigned long long), hipMemcpyDeviceToHost,
                               ctx->stream));
@@ -709,9 +728,9 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     // region (keys were dropped) and is counted again with regions from the exact histogram
     int redone = 0;
     for (size_t ci = (size_t)first; ci < (size_t)last; ci++) {
-        if (!by_engine2[ci] || !sized_by_sample || h[4 * ci + 3] == 0) continue;
+        if (!J.by_engine2[ci] || !sized_by_sample || h[4 * ci + 3] == 0) continue;
         SP_HIP(ctx, hipMemsetAsync(d_len + 4 * ci, 0, 4 * sizeof(unsigned long long), ctx->stream));
-        rc = sp_count_engine2(ctx, ctx->chroms[ci], kp, lower_count, d_len + 4 * ci, true,
+        rc = sp_count_engine2(ctx, ctx->chroms[ci], J.kp, lower_count, d_len + 4 * ci, true,
                               list_mode ? &ctx->sparse[ci] : nullptr);
         if (rc) return rc;
         redone++;
@@ -723,7 +742,7 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     }
     ctx->c2_recounts += redone;
     for (size_t ci = (size_t)first; ci < (size_t)last; ci++) {
-        if (by_engine2[ci] && h[4 * ci + 3] != 0)
+        if (J.by_engine2[ci] && h[4 * ci + 3] != 0)
             return sp_fail(ctx, SP_ESTATE, "count engine 2: chromosome %zu overran its bucket regions with exact sizes", ci);
         ctx->chroms[ci].length_sum = (int64_t)h[4 * ci];
         ctx->chroms[ci].n_dump = (int64_t)h[4 * ci + 1];

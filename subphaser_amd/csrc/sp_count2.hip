@@ -24,31 +24,15 @@
 //   0.625 x2 (scans) + 3 w + 3 r + 2 w + 2 r + 1 x slots/base (table write).
 #include "sp_device.h"
 #include "sp_c2batch.h"
+#include "sp_c2plan.h"
 #include "sp_internal.h"
 #include "sp_swar.h"
 
-#define C2_B3 15                      // slot bits resolved inside LDS
-#define C2_FINE (1 << C2_B3)          // slots per fine bucket
-#ifndef C2_P1_THREADS
-#define C2_P1_THREADS 512             // part1: 512 threads x 32 k-mer starts
-#endif
-#define C2_P1_UNIT 32
 #define C2_P1_KEYS (C2_P1_THREADS * C2_P1_UNIT)   // starts (<= keys) per part1 tile
-#ifndef C2_P2_THREADS
-#define C2_P2_THREADS 256             // (round 4, after the cursor fix: 256 x 24: 0.861 ms, 512 x 24: 0.897, 512 x 16: 0.990, 768 x 16: 1.20) part2 tile = threads x keys per thread.  Round 1 (software pipeline): 512 x 8 -> 1.37 ms per
-                                      // 667-Mb chromosome, 768 x 12 -> 1.22.  Round 2 (rank from the histogram atomic, one table read
-                                      // in the copy-out): 768 x 12 1.21, 768 x 16 1.31, 768 x 20 1.25, 1024 x 12 1.23, 1024 x 16 1.17,
-                                      // 512 x 24 1.16 (adopted: 12 K-key tiles, 288-byte runs, three blocks per CU)
-#endif
-#ifndef C2_P2_PER
-#define C2_P2_PER 24
-#endif
-#define C2_TILE_KEYS (C2_P2_THREADS * C2_P2_PER)  // keys per part2 tile
 #ifndef C2_P2_SPREAD
 #define C2_P2_SPREAD 128              // part2 tile order: concurrently processed tiles lie n_tiles / 128 apart
 #endif
 #define C2_HIST_THREADS 512
-#define C2_MAXF 128                   // max fan-out per level (k <= 15: at most 2^29 slots = 7 + 7 + 15 bits)
 #define C2_DROP (~0ULL)               // delta / gbase of a run that does not fit its region (estimate mode)
 // Records travel in QUADS (round 4).  A bucket run written by one tile is padded to a multiple of four records, so that
 // the copy-out of both partition kernels handles four consecutive records per lane: one 16-byte LDS read, one look-up
@@ -59,22 +43,6 @@
 #define C2_INVALID1 0xFFFFFFu
 #define C2_INVALID2 0xFFFFu
 #define C2_PADS (3 * C2_MAXF)         // pad records one tile can add at most
-// Cursors (round 4, tools/ubench_frag.hip).  Returning atomics on ONE cache line serialise: 128 cursors packed into
-// 1 KiB held a 40 K-tile partition pass at 0.88 ms whatever it wrote; one cursor per 128-byte line 0.52 ms; eight
-// sub-cursors per bucket on a line each 0.29 ms.  So every cursor owns a line, and a level-1 bucket is cut into
-// C2_SPLIT sub-regions with a cursor each: tile t appends to sub-region t mod C2_SPLIT (a static, even deal of the
-// tiles; with the blocks of a launch dealt round-robin to the XCDs, usually also a deal by L2).  Downstream a
-// sub-region is just a level-1 "bucket" of its own: V1 = F1 * C2_SPLIT of them.
-#define C2_SPLIT 8
-#define C2_CSTRIDE 16                 // cursor stride in 8-byte words
-#define C2_MAXV (C2_MAXF * C2_SPLIT)
-// Layout (measured on one 667-Mb chain, part1 / part2 ms): every cursor on a line of its own 0.922 / 0.953; the 128
-// cursors that ONE tile touches packed together -- sub-region m of all buckets in 1 KiB, the sub-regions apart --
-// 0.883 / 0.899: a wave's atomics then touch 8 lines instead of 64, and only the tiles of one residue class (part1) or of
-// one level-1 bucket (part2, whose concurrent tiles lie in different buckets) share them.
-#ifndef C2_CSTRIDE2
-#define C2_CSTRIDE2 1                 // stride of the fine (part2) cursors
-#endif
 // where the cursor of level-1 sub-region vb = b * C2_SPLIT + m lives (8-byte words)
 #ifndef C2_CUR1_PACKED
 #define C2_CUR1_PACKED 1
@@ -85,35 +53,10 @@
 #define C2_CUR1(vb) ((size_t)(vb) * C2_CSTRIDE)
 #endif
 
-struct c2_plan {
-    int T;        // log2(nslots)
-    int B1, B2;   // partition bits
-    int F1, F2;
-    int64_t n_fine;  // F1*F2
-};
-
-static bool c2_make_plan(int64_t nslots, c2_plan &p) {
-    int T = 0;
-    while ((1LL << T) < nslots) T++;
-    if ((1LL << T) != nslots) return false;
-    int R = T - C2_B3;
-    if (R < 2) return false;
-    p.T = T;
-    p.B1 = (R + 1) / 2;
-    p.B2 = R / 2;
-    if (p.B1 > 7 || p.B2 > 7) return false;
-    p.F1 = 1 << p.B1;
-    p.F2 = 1 << p.B2;
-    p.n_fine = (int64_t)p.F1 * p.F2;
-    return true;
-}
-
 // ---------------------------------------------------------------- c2_hist_fine
 // Fine histogram (top B1+B2 slot bits) over the units of 32 starts, all of them (sample_shift = 0: exact bucket
 // sizes) or one stripe of C2_STRIPE units in every 2^sample_shift stripes (an estimate).  The sampled stripe of a
 // group rotates with the group index so that no period of the sequence can hide from the sample.
-#define C2_STRIPE 64                  // units per stripe: 2048 starts = 512 B of each packed stream, one wave
-#define C2_SAMPLE_SHIFT 4             // one stripe in 16
 __device__ __forceinline__ int64_t c2_sample_unit(int64_t j, int sample_shift) {
     if (sample_shift == 0) return j;
     const int64_t g = j / C2_STRIPE;                      // sampled stripe number = stripe group
@@ -1521,6 +1464,26 @@ c2_count_list_b(const c2_bdesc *__restrict__ desc, int64_t n_fine, uint32_t lowe
 }
 
 
+// the sizing of a chromosome with the test hooks SP_C2_MULT8 / SP_C2_SLACK (they force overruns) read from the environment
+static c2_sizing c2_size_env(const c2_plan &P, int64_t len, bool exact) {
+    const char *env_mult = getenv("SP_C2_MULT8"), *env_slack = getenv("SP_C2_SLACK");
+    return c2_size(P, len, exact, env_mult ? atoll(env_mult) : -1, env_slack ? atoll(env_slack) : -1);
+}
+
+// a lane's workspace grows to `total` bytes (what is queued on the stream may still be working in the old one)
+static int c2_ws_ensure(sp_ctx *ctx, void *&d_ws2, int64_t &ws2_bytes, size_t total) {
+    if ((int64_t)total <= ws2_bytes) return SP_OK;
+    if (d_ws2) {
+        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        SP_HIP(ctx, hipFree(d_ws2));
+        d_ws2 = nullptr;
+        ws2_bytes = 0;
+    }
+    SP_HIP(ctx, hipMalloc(&d_ws2, total));
+    ws2_bytes = (int64_t)total;
+    return SP_OK;
+}
+
 bool sp_engine2_supported(int64_t nslots) {
     c2_plan p;
     return c2_make_plan(nslots, p);
@@ -1543,152 +1506,85 @@ int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower, 
         return SP_OK;
     }
     const size_t nf = (size_t)P.n_fine;
-    const int64_t n_units32 = (c.len + C2_P1_UNIT - 1) / C2_P1_UNIT;
-    const int64_t n_tiles = (n_units32 + C2_P1_THREADS - 1) / C2_P1_THREADS;   // 16384 starts each
-    // estimate mode: cap(f) = sample(f) * 16 * 9/8 + slack.  The slack absorbs what a 1-in-16 stripe sample cannot
-    // see: a local array of one repeat shorter than 16 stripes (32 K starts) that falls between sampled stripes.
-    const char *env_mult = getenv("SP_C2_MULT8"), *env_slack = getenv("SP_C2_SLACK");   // test hooks (force overruns)
-    const int sample_shift = exact ? 0 : C2_SAMPLE_SHIFT;
-    unsigned long long mult8 = exact ? 8ULL : (unsigned long long)(env_mult ? atoll(env_mult) : (9 << C2_SAMPLE_SHIFT));
-    unsigned long long slack = 0;
-    if (!exact) {
-        int64_t sl = c.len / 64;
-        sl = sl < 4096 ? 4096 : (sl > 32768 ? 32768 : sl);
-        slack = (unsigned long long)(env_slack ? atoll(env_slack) : sl);
-    }
-    const unsigned long long slack1 = env_slack ? slack : 4ULL * slack + 65536ULL;
-    const unsigned long long mult8_1 = (exact || env_mult) ? mult8 : (unsigned long long)(33 << (C2_SAMPLE_SHIFT - 2));   // x 1 1/32
-    const int64_t n_stripes = (n_units32 + C2_STRIPE - 1) / C2_STRIPE;
-    const int64_t n_visit = exact ? n_units32 : ((n_stripes + (1 << C2_SAMPLE_SHIFT) - 1) >> C2_SAMPLE_SHIFT) * C2_STRIPE;
-    // keys the regions can hold at most (rigorous bounds: the sample sees at most n_visit * 32 k-mers).  Pad records:
-    // three per (part1 tile, level-1 bucket) and per (part2 tile, fine bucket) at most -- c2_offsets adds the same terms.
-    const unsigned long long pad1 = 3ULL * (unsigned long long)n_tiles + 3ULL * C2_SPLIT;
-    // estimate mode: C2_SPLIT sub-regions per level-1 bucket, a quarter of the bucket's slack each; exact mode: one
-    const int split = exact ? 1 : C2_SPLIT;
-    const unsigned long long sslack = exact ? 0ULL : slack1 / 4;
     const int V1 = P.F1 * C2_SPLIT;
-    const size_t cap_keys1 = (exact ? (size_t)c.len : (size_t)(((unsigned long long)n_visit * C2_P1_UNIT * mult8_1 + 7) / 8) +
-                                                          (size_t)P.F1 * (size_t)slack1) + (size_t)P.F1 * (size_t)(pad1 + 4) +
-                             (size_t)V1 * (size_t)(sslack + 8);
-    const size_t tiles2_max = cap_keys1 / C2_TILE_KEYS + 2 * (size_t)V1;
-    const size_t cap_keys2 = (exact ? (size_t)c.len + 4 * nf
-                                    : (size_t)(((unsigned long long)n_visit * C2_P1_UNIT * mult8 + 7) / 8) + nf * (size_t)(slack + 4)) +
-                             3 * (size_t)P.F2 * tiles2_max;
-    const size_t cap_keys = cap_keys1 > cap_keys2 ? cap_keys1 : cap_keys2;
-    // workspace: ghist | off_fine | off1 | tile_start | cursor1 | cursor2 | level-1 planes (3 B / key) | buf2 (u16 / key)
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    size_t o_ghist = 0;
-    size_t o_offf = o_ghist + al(nf * 8);
-    size_t o_off1 = o_offf + al((nf + 1) * 8);
-    size_t o_tile = o_off1 + al((size_t)(V1 + 1) * 16);         // level-1 sub-region starts, then ends
-    size_t o_cur1 = o_tile + al((size_t)(V1 + 1) * 8);
-    size_t o_cur2 = o_cur1 + al((size_t)C2_MAXV * 8 * C2_CSTRIDE);   // (any layout of C2_CUR1: sub-region m of bucket b)
-    size_t o_tcnt = o_cur2 + al(nf * 8 * C2_CSTRIDE2);           // end of the zeroed head of the workspace
-    size_t o_span = o_tcnt;
-    o_tcnt = o_span + al(nf * 16);              // (the spans are written before they are read: not zeroed)
-    const size_t zero_bytes = o_span;
-    const size_t lo1_bytes = al(cap_keys1 * 2 + 64 + (size_t)V1 * 8);
-    size_t o_buf1 = o_tcnt;
-    size_t o_buf2 = o_buf1 + lo1_bytes + al(cap_keys1 + 64 + (size_t)V1 * 4);
-    size_t o_segb = o_buf2 + al(cap_keys2 * 2 + 64);               // overflow segments: base, count, offsets per fine bucket
-    size_t o_segc = o_segb + al(nf * 4);
-    size_t o_sego = o_segc + al(nf * 4);
-    size_t o_bigl = o_sego + al((nf + 1) * 4);                    // (unused since round 6: c2_count16 keeps every bucket)
-    size_t total = o_bigl + al(nf * 4);
+    const c2_sizing S = c2_size_env(P, c.len, exact);
+    const size_t cap_keys = S.cap_keys();
     void *&d_ws2 = ctx->lane ? ctx->lane->d_ws2 : ctx->d_ws2;           // this lane's workspace (sp_common.h)
     int64_t &ws2_bytes = ctx->lane ? ctx->lane->ws2_bytes : ctx->ws2_bytes;
     sp_buf &b_ovfw = ctx->lane ? ctx->lane->b_ovfw : ctx->b_ovfw;
-    if ((int64_t)total > ws2_bytes) {
-        if (d_ws2) {
-            SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            SP_HIP(ctx, hipFree(d_ws2));
-            d_ws2 = nullptr;
-            ws2_bytes = 0;
-        }
-        SP_HIP(ctx, hipMalloc(&d_ws2, total));
-        ws2_bytes = (int64_t)total;
-    }
-    char *ws = (char *)d_ws2;
-    unsigned long long *ghist = (unsigned long long *)(ws + o_ghist);
-    unsigned long long *off_fine = (unsigned long long *)(ws + o_offf);
-    unsigned long long *off1 = (unsigned long long *)(ws + o_off1);
-    unsigned long long *tile_start = (unsigned long long *)(ws + o_tile);
-    unsigned long long *cur1 = (unsigned long long *)(ws + o_cur1), *cur2 = (unsigned long long *)(ws + o_cur2);
-    uint16_t *buf2 = (uint16_t *)(ws + o_buf2);
-    uint32_t *seg_base = (uint32_t *)(ws + o_segb), *seg_cnt = (uint32_t *)(ws + o_segc), *seg_off = (uint32_t *)(ws + o_sego);
-    uint16_t *lo1 = (uint16_t *)(ws + o_buf1);                         // level-1 records: 3 bytes per key in two planes
-    uint8_t *hi1 = (uint8_t *)(ws + o_buf1) + lo1_bytes;
+    sp_carve sizer;
+    c2_lay(P, S, 0, sizer, sizer);
+    int rcw = c2_ws_ensure(ctx, d_ws2, ws2_bytes, sizer.off);
+    if (rcw) return rcw;
+    sp_carve w(d_ws2);
+    const c2_layout L = c2_lay(P, S, 0, w, w);
+    uint32_t *seg_base = L.seg_base, *seg_cnt = L.seg_cnt, *seg_off = L.seg_off;
+    const uint16_t *buf2 = L.buf2;
+    const ulonglong2 *span = (const ulonglong2 *)L.span;
     // the unordered overflow pairs live in the level-1 planes (dead once part2 has run); an engine-3 (list) run stages every
     // kept slot and gets a buffer of its own
     // (a bucket's segment starts at floor(its first key / L), L = 255 or lower_count: cap_keys / L pairs at most)
-    uint2 *ovf_tmp = (uint2 *)(ws + o_buf1);
-    unsigned long long ovf_cap = (unsigned long long)(lo1_bytes / 8);
+    uint2 *ovf_tmp = (uint2 *)L.lo1;
+    unsigned long long ovf_cap = (unsigned long long)(L.lo1_bytes() / 8);
     if (list && c.len >= (1LL << 32) - 16)
         return sp_fail(ctx, SP_EUNSUP, "count engine 3: a chromosome of %lld bases (32-bit positions inside a bucket)", (long long)c.len);
     if (cap_keys / (size_t)(list ? lower : 255) + C2_FINE >= ((size_t)1 << 32))
         return sp_fail(ctx, SP_EUNSUP, "count engine 2: a chromosome of %lld bases needs 64-bit segment offsets", (long long)c.len);
     if (list) {
-        const unsigned long long need = (unsigned long long)(cap_keys / (size_t)lower) + C2_FINE + 16;
+        const unsigned long long need = (unsigned long long)S.stage_pairs(lower);
         int rcl = sp_buf_ensure(ctx, b_ovfw, (int64_t)need * 8);
         if (rcl) return rcl;
         ovf_tmp = (uint2 *)b_ovfw.p;
         ovf_cap = need;
     }
-    // zero ghist .. cursor2 in one memset (they are contiguous)
-    SP_HIP(ctx, hipMemsetAsync(ws, 0, zero_bytes, ctx->stream));
+    // zero the head, ghist .. cursor2, in one memset
+    SP_HIP(ctx, hipMemsetAsync(d_ws2, 0, (size_t)((char *)L.span - (char *)d_ws2), ctx->stream));
 
     const sp_kparams32 kp32 = sp_make_kparams32(kp.k);
-    int grid_scan = (int)(n_tiles < (int64_t)ctx->n_cu * 8 ? n_tiles : (int64_t)ctx->n_cu * 8);
+    int grid_scan = (int)(S.n_tiles < (int64_t)ctx->n_cu * 8 ? S.n_tiles : (int64_t)ctx->n_cu * 8);
     size_t sh_hist = nf * 4;
-    const int64_t hist_tiles = (n_visit + C2_P1_THREADS - 1) / C2_P1_THREADS;
+    const int64_t hist_tiles = (S.n_visit + C2_P1_THREADS - 1) / C2_P1_THREADS;
     // (every block flushes its LDS histogram with one global atomic per non-empty bin: the sample runs on fewer blocks)
     const int64_t hist_blocks = exact ? (int64_t)ctx->n_cu * 2 : (int64_t)ctx->n_cu / 2;
     int grid_hist = (int)(hist_tiles < hist_blocks ? hist_tiles : hist_blocks);
     if (sh_hist > 48 * 1024)
         SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_hist_fine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_hist));
     SP_LAUNCH(ctx, exact ? "c2_hist_fine" : "c2_hist_sample", c2_hist_fine, dim3(grid_hist), dim3(C2_P1_THREADS), sh_hist,
-              c.d_pk, c.d_pm, c.d_nm, n_units32, n_visit, sample_shift, kp32, C2_B3, (int)nf, ghist);
-    SP_LAUNCH(ctx, "c2_offsets", c2_offsets, dim3(1), dim3(1024), 0, ghist, (int)nf, P.F1, P.F2, mult8, mult8_1, slack, slack1, pad1,
-              split, sslack, off_fine, off1);
-    SP_LAUNCH(ctx, "c2_part1", c2_part1, dim3(grid_scan), dim3(C2_P1_THREADS), 0, c.d_pk, c.d_pm, c.d_nm, n_units32,
-              kp32, P.T - P.B1, P.F1, split, off1, cur1, n_tiles, lo1, hi1);
-    SP_LAUNCH(ctx, "c2_tiles", c2_tiles, dim3(1), dim3(C2_MAXV), 0, (const unsigned long long *)cur1, V1, off1, tile_start,
+              c.d_pk, c.d_pm, c.d_nm, S.n_units32, S.n_visit, S.sample_shift, kp32, C2_B3, (int)nf, L.ghist);
+    SP_LAUNCH(ctx, "c2_offsets", c2_offsets, dim3(1), dim3(1024), 0, L.ghist, (int)nf, P.F1, P.F2, S.mult8, S.mult8_1, S.slack, S.slack1,
+              S.pad1, S.split, S.sslack, L.off_fine, L.off1);
+    SP_LAUNCH(ctx, "c2_part1", c2_part1, dim3(grid_scan), dim3(C2_P1_THREADS), 0, c.d_pk, c.d_pm, c.d_nm, S.n_units32,
+              kp32, P.T - P.B1, P.F1, S.split, L.off1, L.cur1, S.n_tiles, L.lo1, L.hi1);
+    SP_LAUNCH(ctx, "c2_tiles", c2_tiles, dim3(1), dim3(C2_MAXV), 0, (const unsigned long long *)L.cur1, V1, L.off1, L.tile_start,
               d_len4 + 3);
     // part2 grid: enough blocks to cover the tiles (tile count lives on the device; over-provision)
-    int64_t max_tiles2 = (int64_t)tiles2_max;
+    int64_t max_tiles2 = (int64_t)S.tiles2_max;
     int grid2 = (int)(max_tiles2 < (int64_t)ctx->n_cu * 8 ? max_tiles2 : (int64_t)ctx->n_cu * 8);
-    SP_LAUNCH(ctx, "c2_part2", c2_part2, dim3(grid2), dim3(C2_P2_THREADS), 0, (const uint16_t *)lo1, (const uint8_t *)hi1, off1,
-              tile_start, V1,
-              P.F2, C2_B3, off_fine, cur2, buf2);
+    SP_LAUNCH(ctx, "c2_part2", c2_part2, dim3(grid2), dim3(C2_P2_THREADS), 0, (const uint16_t *)L.lo1, (const uint8_t *)L.hi1, L.off1,
+              L.tile_start, V1, P.F2, C2_B3, L.off_fine, L.cur2, L.buf2);
     int gridc = (int)((int64_t)nf < (int64_t)ctx->n_cu ? (int64_t)nf : (int64_t)ctx->n_cu);
-    ulonglong2 *span = (ulonglong2 *)(ws + o_span);
-    SP_LAUNCH(ctx, "c2_spans", c2_spans, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (const unsigned long long *)off_fine,
-              (const unsigned long long *)cur2, (int64_t)nf, span, d_len4 + 3, (uint32_t)(list ? lower : 0));
+    SP_LAUNCH(ctx, "c2_spans", c2_spans, dim3((unsigned)((nf + 255) / 256)), dim3(256), 0, (const unsigned long long *)L.off_fine,
+              (const unsigned long long *)L.cur2, (int64_t)nf, (ulonglong2 *)L.span, d_len4 + 3, (uint32_t)(list ? lower : 0));
     if (list) {
+        auto launch_list = [&](auto kernel, int grid, int threads, int lds) -> int {
+            SP_HIP(ctx, hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+            SP_LAUNCH(ctx, "c2_count_list", kernel, dim3(grid), dim3(threads), lds, buf2, span, (int64_t)nf, (uint32_t)lower, d_len4,
+                      ovf_tmp, ovf_cap, seg_base, seg_cnt);
+            return SP_OK;
+        };
         if ((int64_t)gridc * C2L_MAXB < (int64_t)nf) gridc = (int)(((int64_t)nf + C2L_MAXB - 1) / C2L_MAXB);
         const char *env_l16 = getenv("SP_C2_LIST16");      // "0": the 32-bit list counter everywhere (cross-check)
         if (!exact && !(env_l16 && env_l16[0] == '0')) {
             // (estimate mode only: a bucket of 65536 keys or more raises the overrun flag and the exact recount takes the kernels below)
             int g16 = (int)((int64_t)nf < (int64_t)ctx->n_cu * 2 ? (int64_t)nf : (int64_t)ctx->n_cu * 2);
             if ((int64_t)g16 * C2L_MAXB < (int64_t)nf) g16 = (int)(((int64_t)nf + C2L_MAXB - 1) / C2L_MAXB);
-            if (c.len >= C2L16_MAXLEN) {
-                SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_count_list16<true>, hipFuncAttributeMaxDynamicSharedMemorySize, C2_FINE * 2));
-                SP_LAUNCH(ctx, "c2_count_list", c2_count_list16<true>, dim3(g16), dim3(C2L16_THREADS), C2_FINE * 2, buf2,
-                          (const ulonglong2 *)span, (int64_t)nf, (uint32_t)lower, d_len4, ovf_tmp, ovf_cap, seg_base, seg_cnt);
-            } else {
-                SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_count_list16<false>, hipFuncAttributeMaxDynamicSharedMemorySize, C2_FINE * 2));
-                SP_LAUNCH(ctx, "c2_count_list", c2_count_list16<false>, dim3(g16), dim3(C2L16_THREADS), C2_FINE * 2, buf2,
-                          (const ulonglong2 *)span, (int64_t)nf, (uint32_t)lower, d_len4, ovf_tmp, ovf_cap, seg_base, seg_cnt);
-            }
-        } else if (c.len >= (1LL << 26)) {
-            SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_count_list<true>, hipFuncAttributeMaxDynamicSharedMemorySize, C2_FINE * 4));
-            SP_LAUNCH(ctx, "c2_count_list", c2_count_list<true>, dim3(gridc), dim3(C2_COUNT_THREADS), C2_FINE * 4, buf2,
-                      (const ulonglong2 *)span, (int64_t)nf, (uint32_t)lower, d_len4, ovf_tmp, ovf_cap, seg_base, seg_cnt);
+            rcw = c.len >= C2L16_MAXLEN ? launch_list(c2_count_list16<true>, g16, C2L16_THREADS, C2_FINE * 2)
+                                        : launch_list(c2_count_list16<false>, g16, C2L16_THREADS, C2_FINE * 2);
         } else {
-            SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_count_list<false>, hipFuncAttributeMaxDynamicSharedMemorySize, C2_FINE * 4));
-            SP_LAUNCH(ctx, "c2_count_list", c2_count_list<false>, dim3(gridc), dim3(C2_COUNT_THREADS), C2_FINE * 4, buf2,
-                      (const ulonglong2 *)span, (int64_t)nf, (uint32_t)lower, d_len4, ovf_tmp, ovf_cap, seg_base, seg_cnt);
+            rcw = c.len >= (1LL << 26) ? launch_list(c2_count_list<true>, gridc, C2_COUNT_THREADS, C2_FINE * 4)
+                                       : launch_list(c2_count_list<false>, gridc, C2_COUNT_THREADS, C2_FINE * 4);
         }
+        if (rcw) return rcw;
         return sp_ovf_finalize_split(ctx, (unsigned long long *)list->d_keys, list->d_cnts, ovf_tmp, seg_base, seg_cnt, seg_off,
                                      (int64_t)nf, d_len4 + 2);
     }
@@ -1707,8 +1603,8 @@ int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower, 
 }
 
 // ---------------------------------------------------------------- engine 3, batched: one launch per kernel type (sp_c2batch.h)
-// Same chain, same layout arithmetic as sp_count_engine2 (estimate mode only: a chromosome whose flag comes back up is
-// counted again, alone, from the exact histogram by the caller).  Workspace: the zeroed heads (histogram .. cursors) of all
+// The chain of sp_count_engine2 (estimate mode only: a chromosome whose flag comes back up is counted again, alone, from
+// the exact histogram by the caller).  Workspace: the descriptor table, the zeroed heads (histogram .. cursors) of all
 // chromosomes back to back -- one memset -- then their bodies.
 int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kparams &kp, int lower, unsigned long long *d_len /* 4 per chromosome */) {
     c2_plan P;
@@ -1716,58 +1612,25 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
         return sp_fail(ctx, SP_EUNSUP, "count engine 3 needs a dense slot space of 2^17..2^31 slots (k=%d)", kp.k);
     const size_t nf = (size_t)P.n_fine;
     const int V1 = P.F1 * C2_SPLIT;
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    // head (zeroed): ghist | off_fine | off1 | tile_start | cursor1 | cursor2
-    const size_t h_ghist = 0, h_offf = h_ghist + al(nf * 8), h_off1 = h_offf + al((nf + 1) * 8),
-                 h_tile = h_off1 + al((size_t)(V1 + 1) * 16), h_cur1 = h_tile + al((size_t)(V1 + 1) * 8),
-                 h_cur2 = h_cur1 + al((size_t)C2_MAXV * 8 * C2_CSTRIDE), head_bytes = h_cur2 + al(nf * 8 * C2_CSTRIDE2);
-    const char *env_mult = getenv("SP_C2_MULT8"), *env_slack = getenv("SP_C2_SLACK");   // test hooks (force overruns)
-    std::vector<c2_bdesc> hd((size_t)n);
-    std::vector<size_t> body_off((size_t)n), lo1_bytes_v((size_t)n), k1((size_t)n), k2((size_t)n), stage_n((size_t)n);
-    size_t body_total = 0;
+    std::vector<c2_sizing> sz((size_t)n);
+    std::vector<size_t> body_off((size_t)n + 1);      // where every chromosome's body starts among the bodies; their end
+    sp_carve desc_sizer, head_sizer, body_sizer;
+    desc_sizer.take<c2_bdesc>((size_t)n);
     int64_t max_tiles = 0, max_hist_tiles = 0, max_tiles2 = 0;
     for (int i = 0; i < n; i++) {
         const sp_chrom &c = ctx->chroms[(size_t)chrom_idx[i]];
-        c2_bdesc &D = hd[(size_t)i];
-        D.pk = c.d_pk;
-        D.pm = c.d_pm;
-        D.nm = c.d_nm;
-        D.n_units32 = (c.len + C2_P1_UNIT - 1) / C2_P1_UNIT;
-        D.n_tiles = (D.n_units32 + C2_P1_THREADS - 1) / C2_P1_THREADS;
-        D.sample_shift = C2_SAMPLE_SHIFT;
-        D.mult8 = (unsigned long long)(env_mult ? atoll(env_mult) : (9 << C2_SAMPLE_SHIFT));
-        int64_t sl = c.len / 64;
-        sl = sl < 4096 ? 4096 : (sl > 32768 ? 32768 : sl);
-        D.slack = (unsigned long long)(env_slack ? atoll(env_slack) : sl);
-        D.slack1 = env_slack ? D.slack : 4ULL * D.slack + 65536ULL;
-        D.mult8_1 = env_mult ? D.mult8 : (unsigned long long)(33 << (C2_SAMPLE_SHIFT - 2));
-        const int64_t n_stripes = (D.n_units32 + C2_STRIPE - 1) / C2_STRIPE;
-        D.n_visit = ((n_stripes + (1 << C2_SAMPLE_SHIFT) - 1) >> C2_SAMPLE_SHIFT) * C2_STRIPE;
-        D.pad1 = 3ULL * (unsigned long long)D.n_tiles + 3ULL * C2_SPLIT;
-        D.split = C2_SPLIT;
-        D.sslack = D.slack1 / 4;
-        const size_t cap_keys1 = (size_t)(((unsigned long long)D.n_visit * C2_P1_UNIT * D.mult8_1 + 7) / 8) + (size_t)P.F1 * (size_t)D.slack1 +
-                                 (size_t)P.F1 * (size_t)(D.pad1 + 4) + (size_t)V1 * (size_t)(D.sslack + 8);
-        const size_t tiles2_max = cap_keys1 / C2_TILE_KEYS + 2 * (size_t)V1;
-        const size_t cap_keys2 = (size_t)(((unsigned long long)D.n_visit * C2_P1_UNIT * D.mult8 + 7) / 8) + nf * (size_t)(D.slack + 4) +
-                                 3 * (size_t)P.F2 * tiles2_max;
-        const size_t cap_keys = cap_keys1 > cap_keys2 ? cap_keys1 : cap_keys2;
-        if (c.len >= (1LL << 32) - 16 || cap_keys / (size_t)lower + C2_FINE >= ((size_t)1 << 32))
+        const c2_sizing &S = sz[(size_t)i] = c2_size_env(P, c.len, false);
+        if (c.len >= (1LL << 32) - 16 || S.cap_keys() / (size_t)lower + C2_FINE >= ((size_t)1 << 32))
             return sp_fail(ctx, SP_EUNSUP, "count engine 3: a chromosome of %lld bases", (long long)c.len);
-        k1[(size_t)i] = cap_keys1;
-        k2[(size_t)i] = cap_keys2;
-        stage_n[(size_t)i] = cap_keys / (size_t)lower + C2_FINE + 16;
-        lo1_bytes_v[(size_t)i] = al(cap_keys1 * 2 + 64 + (size_t)V1 * 8);
-        // body: span | level-1 planes | buf2 | seg_base | seg_cnt | seg_off | stage
-        body_off[(size_t)i] = body_total;
-        body_total += al(nf * 16) + lo1_bytes_v[(size_t)i] + al(cap_keys1 + 64 + (size_t)V1 * 4) + al(cap_keys2 * 2 + 64) + 2 * al(nf * 4) +
-                      al((nf + 1) * 4) + al(stage_n[(size_t)i] * 8);
-        if (D.n_tiles > max_tiles) max_tiles = D.n_tiles;
-        const int64_t ht = (D.n_visit + C2_P1_THREADS - 1) / C2_P1_THREADS;
+        body_off[(size_t)i] = body_sizer.off;
+        c2_lay(P, S, S.stage_pairs(lower), head_sizer, body_sizer);
+        if (S.n_tiles > max_tiles) max_tiles = S.n_tiles;
+        const int64_t ht = (S.n_visit + C2_P1_THREADS - 1) / C2_P1_THREADS;
         if (ht > max_hist_tiles) max_hist_tiles = ht;
-        if ((int64_t)tiles2_max > max_tiles2) max_tiles2 = (int64_t)tiles2_max;
+        if ((int64_t)S.tiles2_max > max_tiles2) max_tiles2 = (int64_t)S.tiles2_max;
     }
-    const size_t total = al((size_t)n * sizeof(c2_bdesc)) + (size_t)n * head_bytes + body_total;
+    body_off[(size_t)n] = body_sizer.off;
+    const size_t head_bytes = head_sizer.off / (size_t)n, total = desc_sizer.off + head_sizer.off + body_sizer.off;
     void *&d_ws2 = ctx->lane ? ctx->lane->d_ws2 : ctx->d_ws2;           // this lane's workspace (sp_common.h)
     int64_t &ws2_bytes = ctx->lane ? ctx->lane->ws2_bytes : ctx->ws2_bytes;
     {   // Every chromosome's workspace carries fixed slack per bucket (~0.8 GB at k = 15, whatever its length): hundreds of
@@ -1781,12 +1644,13 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
                                   ? (int64_t)free_b + ws2_bytes - (int64_t)(total_b / 16) : (int64_t)total;
         if (n > 1 && (int64_t)total > avail) {
             const int64_t budget = avail < C2_SPLIT_BYTES ? avail : C2_SPLIT_BYTES;
+            sp_carve one_desc;
+            one_desc.take<c2_bdesc>(1);
             for (int i0 = 0; i0 < n;) {
-                int64_t acc = (int64_t)al(sizeof(c2_bdesc));
+                int64_t acc = (int64_t)one_desc.off;
                 int i1 = i0;
                 while (i1 < n) {
-                    const int64_t per = (int64_t)(al(sizeof(c2_bdesc)) + head_bytes +
-                                                  ((i1 + 1 < n ? body_off[(size_t)i1 + 1] : body_total) - body_off[(size_t)i1]));
+                    const int64_t per = (int64_t)(one_desc.off + head_bytes + (body_off[(size_t)i1 + 1] - body_off[(size_t)i1]));
                     if (i1 > i0 && acc + per > budget) break;
                     acc += per;
                     i1++;
@@ -1800,46 +1664,28 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
             return SP_OK;
         }
     }
-    if ((int64_t)total > ws2_bytes) {
-        if (d_ws2) {
-            SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-            SP_HIP(ctx, hipFree(d_ws2));
-            d_ws2 = nullptr;
-            ws2_bytes = 0;
-        }
-        SP_HIP(ctx, hipMalloc(&d_ws2, total));
-        ws2_bytes = (int64_t)total;
-    }
-    char *ws = (char *)d_ws2;
-    c2_bdesc *d_desc = (c2_bdesc *)ws;
-    char *heads = ws + al((size_t)n * sizeof(c2_bdesc)), *bodies = heads + (size_t)n * head_bytes;
+    const int rcw = c2_ws_ensure(ctx, d_ws2, ws2_bytes, total);
+    if (rcw) return rcw;
+    c2_bdesc *d_desc = (c2_bdesc *)d_ws2;
+    char *heads = (char *)d_ws2 + desc_sizer.off;
+    sp_carve head(heads), body(heads + head_sizer.off);
+    std::vector<c2_bdesc> hd((size_t)n);
     for (int i = 0; i < n; i++) {
+        const sp_chrom &c = ctx->chroms[(size_t)chrom_idx[i]];
+        const c2_sizing &S = sz[(size_t)i];
+        const c2_layout L = c2_lay(P, S, S.stage_pairs(lower), head, body);
+        const sp_sparse_chrom &o = ctx->sparse[(size_t)chrom_idx[i]];
         c2_bdesc &D = hd[(size_t)i];
-        char *h = heads + (size_t)i * head_bytes, *b = bodies + body_off[(size_t)i];
-        D.ghist = (unsigned long long *)(h + h_ghist);
-        D.off_fine = (unsigned long long *)(h + h_offf);
-        D.off1 = (unsigned long long *)(h + h_off1);
-        D.tile_start = (unsigned long long *)(h + h_tile);
-        D.cur1 = (unsigned long long *)(h + h_cur1);
-        D.cur2 = (unsigned long long *)(h + h_cur2);
-        D.span = (ulonglong2 *)b;
-        b += al(nf * 16);
-        D.lo1 = (uint16_t *)b;
-        D.hi1 = (uint8_t *)b + lo1_bytes_v[(size_t)i];
-        b += lo1_bytes_v[(size_t)i] + al(k1[(size_t)i] + 64 + (size_t)V1 * 4);
-        D.buf2 = (uint16_t *)b;
-        b += al(k2[(size_t)i] * 2 + 64);
-        D.seg_base = (uint32_t *)b;
-        b += al(nf * 4);
-        D.seg_cnt = (uint32_t *)b;
-        b += al(nf * 4);
-        D.seg_off = (uint32_t *)b;
-        b += al((nf + 1) * 4);
-        D.stage = (uint2 *)b;
-        D.stage_cap = (unsigned long long)stage_n[(size_t)i];
+        D.pk = c.d_pk, D.pm = c.d_pm, D.nm = c.d_nm;
+        D.n_units32 = S.n_units32, D.n_visit = S.n_visit, D.n_tiles = S.n_tiles;
+        D.sample_shift = S.sample_shift, D.split = S.split;
+        D.mult8 = S.mult8, D.mult8_1 = S.mult8_1, D.slack = S.slack, D.slack1 = S.slack1, D.pad1 = S.pad1, D.sslack = S.sslack;
+        D.ghist = L.ghist, D.off_fine = L.off_fine, D.off1 = L.off1, D.tile_start = L.tile_start, D.cur1 = L.cur1, D.cur2 = L.cur2;
+        D.span = (ulonglong2 *)L.span, D.lo1 = L.lo1, D.hi1 = L.hi1, D.buf2 = L.buf2;
+        D.seg_base = L.seg_base, D.seg_cnt = L.seg_cnt, D.seg_off = L.seg_off;
+        D.stage = (uint2 *)L.stage, D.stage_cap = (unsigned long long)S.stage_pairs(lower);
         D.d_len4 = d_len + 4 * (size_t)chrom_idx[i];
-        D.out_keys = (unsigned long long *)ctx->sparse[(size_t)chrom_idx[i]].d_keys;
-        D.out_cnts = ctx->sparse[(size_t)chrom_idx[i]].d_cnts;
+        D.out_keys = (unsigned long long *)o.d_keys, D.out_cnts = o.d_cnts;
     }
     // the table travels from a page-locked buffer of this lane's (advisor r05: a pageable source is only safe because the
     // runtime stages it before hipMemcpyAsync returns -- and that staging made the host wait on the lane's stream).  The
@@ -1859,7 +1705,7 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
     }
     memcpy(h_desc, hd.data(), (size_t)n * sizeof(c2_bdesc));
     SP_HIP(ctx, hipMemcpyAsync(d_desc, h_desc, (size_t)n * sizeof(c2_bdesc), hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemsetAsync(heads, 0, (size_t)n * head_bytes, ctx->stream));
+    SP_HIP(ctx, hipMemsetAsync(heads, 0, head_sizer.off, ctx->stream));
     const sp_kparams32 kp32 = sp_make_kparams32(kp.k);
     const unsigned un = (unsigned)n;
     // grids: what the largest chromosome needs, capped so that all chromosomes together fill the chip a few times over

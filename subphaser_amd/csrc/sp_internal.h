@@ -17,6 +17,9 @@ int sp_ovf_finalize(sp_ctx *ctx, sp_chrom &c, const uint2 *tmp, const uint32_t *
 int sp_ovf_finalize_split(sp_ctx *ctx, unsigned long long *keys, uint32_t *cnts, const uint2 *tmp, const uint32_t *seg_base,
                           const uint32_t *seg_cnt, uint32_t *seg_off, int64_t n_buckets, unsigned long long *d_total);
 int sp_ovf_finalize_split_batch(sp_ctx *ctx, const c2_bdesc *d_desc, int n_chrom, int64_t n_buckets);
+int sp_lanes_open(sp_ctx *ctx, int n);      // lanes 0 .. n - 1: stream and `done` event; the context's lane_go event
+int sp_lanes_join(sp_ctx *ctx, int n);      // the context's stream waits for the lanes
+void sp_lanes_drain(sp_ctx *ctx, int n);    // after an error: host wait for the lanes and the context's stream, ctx->err kept
 
 // sp_count2.hip
 bool sp_engine2_supported(int64_t nslots);

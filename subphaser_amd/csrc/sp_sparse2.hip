@@ -24,6 +24,7 @@
 // chromosome at k = 21) are sorted together by one segmented device sort and run-length encoded by s3_big_rle.
 // Bytes per key (k = 21): 0.375 x 3 scans + 4 w + 4 r + 4 r + 4 w + 4 r  ~ 21 B against ~100 B.
 #include "sp_device.h"
+#include "sp_c2plan.h"      // sp_lanes_fit
 #include "sp_internal.h"
 
 #define S3_MAXF 1024
@@ -2115,16 +2116,13 @@ int sp_sparse_count3(sp_ctx *ctx, int k, int lower) {
         const int64_t per_lane = (int64_t)((cap_tot * r2 > l1 ? cap_tot * r2 : l1) + cap_tot * r2 + cap_tot * (r2 + 4.0)) + (64LL << 20);
         size_t free_b = 0, total_b = 0;
         if (hipMemGetInfo(&free_b, &total_b) == hipSuccess) {
-            int64_t budget = (int64_t)free_b - (int64_t)(total_b / 16);      // keep a sixteenth of the device free
-            int fit = 0;
+            int64_t need[SP_MAX_LANES];
             for (int l = 0; l < n_lanes; l++) {
                 const sp_ctx::lane_t &ln = ctx->lanes[l];
                 const int64_t have = ln.b_sp_a.cap + ln.b_sp_b.cap + ln.b_sp_c.cap;
-                const int64_t need = have >= per_lane ? 0 : per_lane - have;
-                if (need > budget) break;
-                budget -= need;
-                fit++;
+                need[l] = have >= per_lane ? 0 : per_lane - have;
             }
+            const int fit = sp_lanes_fit(need, n_lanes, (int64_t)free_b, (int64_t)total_b);
             if (fit < n_lanes) {
                 if (getenv("SP_DEBUG_COUNT")) fprintf(stderr, "[sp] k > 15 count: %d of %d lanes fit the free device memory\n", fit, n_lanes);
                 n_lanes = fit;
@@ -2134,19 +2132,15 @@ int sp_sparse_count3(sp_ctx *ctx, int k, int lower) {
     if (!ctx->h_s3) SP_HIP(ctx, hipHostMalloc((void **)&ctx->h_s3, (size_t)(SP_MAX_LANES + 1) * 8 * sizeof(unsigned long long), hipHostMallocDefault));
     for (auto &e : ctx->s3_ev)
         if (!e) SP_HIP(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    int rc = sp_lanes_open(ctx, n_lanes);
+    if (rc) return rc;
     for (int l = 0; l < n_lanes; l++) {
         sp_ctx::lane_t &ln = ctx->lanes[l];
-        if (!ln.stream) {
-            SP_HIP(ctx, hipStreamCreateWithFlags(&ln.stream, hipStreamNonBlocking));
-            SP_HIP(ctx, hipEventCreateWithFlags(&ln.done, hipEventDisableTiming));
-        }
         if (!ln.ev_a) SP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_a, hipEventDisableTiming));
         if (!ln.ev_b) SP_HIP(ctx, hipEventCreateWithFlags(&ln.ev_b, hipEventDisableTiming));
     }
-    if (n_lanes) {      // chromosomes without an event of their own: the lanes start behind what the main stream holds now
-        if (!ctx->lane_go) SP_HIP(ctx, hipEventCreateWithFlags(&ctx->lane_go, hipEventDisableTiming));
-        SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
-    }
+    // chromosomes without an event of their own: the lanes start behind what the main stream holds now
+    if (n_lanes) SP_HIP(ctx, hipEventRecord(ctx->lane_go, ctx->stream));
     const int n_jobs = n_lanes ? n_lanes : 1;
     std::vector<s3_job> jobs((size_t)n_jobs);
     for (int l = 0; l < n_jobs; l++) {
@@ -2155,17 +2149,9 @@ int sp_sparse_count3(sp_ctx *ctx, int k, int lower) {
         jobs[(size_t)l].ev_b = n_lanes ? ctx->lanes[l].ev_b : ctx->s3_ev[1];
     }
     std::vector<size_t> redo;      // chromosomes whose sampled regions overran: counted again below, exact sizes, one by one
-    hipStream_t main_stream = ctx->stream;
-    // (a lambda: an error return inside must restore the context's stream and let the lanes drain)
     auto on_lane = [&](int l, int phase, s3_job &J) -> int {
-        if (n_lanes) {
-            ctx->lane = &ctx->lanes[l];
-            ctx->stream = ctx->lanes[l].stream;
-        }
-        const int rc = s3_chain(ctx, phase, ctx->chroms[J.ci], ctx->sparse[J.ci], P, kp, lower, J);
-        ctx->lane = nullptr;
-        ctx->stream = main_stream;
-        return rc;
+        sp_ctx::lane_scope on(ctx, n_lanes ? &ctx->lanes[l] : nullptr);
+        return s3_chain(ctx, phase, ctx->chroms[J.ci], ctx->sparse[J.ci], P, kp, lower, J);
     };
     auto finish = [&](int l) -> int {
         s3_job &J = jobs[(size_t)l];
@@ -2204,20 +2190,13 @@ int sp_sparse_count3(sp_ctx *ctx, int k, int lower) {
         }
         return SP_OK;
     };
-    int rc = run_all();
-    ctx->lane = nullptr;
-    ctx->stream = main_stream;
-    if (rc) {
-        const std::string msg = ctx->err;
-        for (int l = 0; l < n_lanes; l++) hipStreamSynchronize(ctx->lanes[l].stream);
-        hipStreamSynchronize(ctx->stream);
-        ctx->err = msg;
+    rc = run_all();
+    if (rc) {      // (an error return inside must let the lanes drain)
+        sp_lanes_drain(ctx, n_lanes);
         return rc;
     }
-    for (int l = 0; l < n_lanes; l++) {      // the main stream goes on when every lane is done
-        SP_HIP(ctx, hipEventRecord(ctx->lanes[l].done, ctx->lanes[l].stream));
-        SP_HIP(ctx, hipStreamWaitEvent(ctx->stream, ctx->lanes[l].done, 0));
-    }
+    rc = sp_lanes_join(ctx, n_lanes);
+    if (rc) return rc;
     for (size_t ci : redo) {
         if (exact0) return sp_fail(ctx, SP_ESTATE, "k > 15: a bucket overran a region of its exact size");
         ctx->c2_recounts++;

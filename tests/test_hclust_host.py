@@ -13,14 +13,13 @@ non-negative terms and can differ only by contraction or vector order in scipy's
 D squares and the root contributes at most one rounding of relative size 2^-53 to the root of the sum on either side, so
 the relative difference is below (D + 2) 2^-52 (derived, not measured)."""
 import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
 import hclust_ref as hc
+import host_check
 from subphaser_amd import heatmap as hm
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -52,29 +51,16 @@ def case(name):
 NAMES = [c[0] for c in CASES]
 
 
-def _host_compiler():
-    for name in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if name and shutil.which(name):
-            return shutil.which(name)
-    return None
-
-
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    cxx = _host_compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++, g++, clang++ or $CXX) on PATH")
     tmp = tmp_path_factory.mktemp("hclust_host")
     blob = [struct.pack("=q", len(NAMES))]
     for name in NAMES:
         pts = case(name)[0]
         blob += [struct.pack("=qq", *pts.shape), np.ascontiguousarray(pts).tobytes()]
-    data, res, exe = tmp / "cases.bin", tmp / "result.bin", tmp / "hclust_host_check"
+    data, res = tmp / "cases.bin", tmp / "result.bin"
     data.write_bytes(b"".join(blob))
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "subphaser_amd", "csrc"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "hclust_host_check.cpp"), "-lm"])
-    r = subprocess.run([str(exe), str(data), str(res)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = host_check.run(tmp, "hclust_host_check", [data, res], flags=["-ffp-contract=off"], libs=["-lm"])
     assert r.returncode == 0, r.stdout[-2000:]
     raw = res.read_bytes()
     got, at = {}, 0

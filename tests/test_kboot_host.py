@@ -9,35 +9,21 @@ The twin itself is held against scikit-learn statistically: on a separable and a
 R = 400 replicates of 400 columns, the same columns for both) the support columns a (twin) and b (scikit-learn loop),
 in percentage points, must satisfy |a - b| <= 5 sqrt((a (100 - a) + b (100 - b)) / R) + 1: five standard deviations of
 the difference of two binomial shares plus one point for the truncation to integers."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import kboot_ref as kr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 # (C, K, n columns, replicates): the shapes of the GPU test, and K = 1
 SHAPES = [(2, 2, 50, 30), (3, 3, 50, 30), (5, 1, 40, 10), (12, 3, 400, 40), (21, 3, 1000, 40), (33, 4, 100, 20),
           (64, 7, 300, 20), (128, 32, 200, 6)]
 
 
-def _host_compiler():
-    for name in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if name and shutil.which(name):
-            return shutil.which(name)
-    return None
-
-
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    cxx = _host_compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++, g++, clang++ or $CXX) on PATH")
     tmp = tmp_path_factory.mktemp("kboot_host")
     cases, blob = [], []
     for i, (C, K, n, R) in enumerate(SHAPES):
@@ -54,11 +40,7 @@ def host_run(tmp_path_factory):
     data = tmp / "cases.bin"
     data.write_bytes(struct.pack("=q", n_cases) + b"".join(blob) + struct.pack("=q", len(draws))
                      + b"".join(struct.pack("=QQQ", *d) for d in draws))
-    exe = tmp / "kboot_host_check"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "subphaser_amd", "csrc"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "kboot_host_check.cpp"), "-lm"])
-    r = subprocess.run([str(exe), str(data)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = host_check.run(tmp, "kboot_host_check", [data], flags=["-ffp-contract=off"], libs=["-lm"])
     assert r.returncode == 0, r.stdout[-2000:]
     return r.stdout.splitlines(), cases, draws
 

@@ -13,17 +13,14 @@ with planted subgenome structure.  The two differ by rounding only, amplified by
 has a close neighbour, sets it.
 
 Derivable check: every good row adds z . z = C up to rounding, so trace(G) = C (M - n_bad) within 4 C M 2^-52 C."""
-import os
-import shutil
 import struct
-import subprocess
 
 import numpy as np
 import pytest
 
+import host_check
 import kpca_ref as kp
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 TOL = 3.1e-10         # 100 x the measured twin-vs-sklearn difference (never looser than 1e-6)
 
 # (seed, M, C, n_comp, extreme, bad rows, dup)
@@ -37,13 +34,6 @@ CASES = [
 ]
 
 
-def _host_compiler():
-    for name in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if name and shutil.which(name):
-            return shutil.which(name)
-    return None
-
-
 def _inputs():
     out = []
     for seed, M, C, n_comp, extreme, bad, dup in CASES:
@@ -55,21 +45,15 @@ def _inputs():
 
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    cxx = _host_compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++, g++, clang++ or $CXX) on PATH")
     tmp = tmp_path_factory.mktemp("kpca_host")
     inputs = _inputs()
     blob = [struct.pack("=q", len(inputs))]
     for counts, lengths, U in inputs:
         blob += [struct.pack("=qqq", counts.shape[0], counts.shape[1], U.shape[1]), lengths.tobytes(),
                  np.ascontiguousarray(counts).tobytes(), np.ascontiguousarray(U).tobytes()]
-    data, res, exe = tmp / "cases.bin", tmp / "result.bin", tmp / "kpca_host_check"
+    data, res = tmp / "cases.bin", tmp / "result.bin"
     data.write_bytes(b"".join(blob))
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "subphaser_amd", "csrc"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "kpca_host_check.cpp"), "-lm"])
-    r = subprocess.run([str(exe), str(data), str(res)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = host_check.run(tmp, "kpca_host_check", [data, res], flags=["-ffp-contract=off"], libs=["-lm"])
     assert r.returncode == 0, r.stdout[-2000:]
     raw = res.read_bytes()
     got, at = [], 0

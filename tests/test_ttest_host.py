@@ -5,31 +5,20 @@ built).  It must reproduce np.sum bit for bit through the streaming pairwise acc
 the lengths around 4096, 8192 and 65536, magnitudes from 1e-9 to 1e3, one all-positive and one signed vector per length --
 and its sp_tt_pvalue(df, t) must lie within the tolerances of tests/hp_reference.py of mpmath's regularised incomplete
 beta for 400 values of t at each df in {1, 2, 3, 10, 127, 129, 1000, 4094, 16382, 65534, 200000}."""
-import os
-import shutil
 import struct
-import subprocess
 
 import mpmath as mp
 import numpy as np
 import pytest
 
+import host_check
 import hp_reference as hr
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 SIZES = list(range(1, 1101)) + [4095, 4096, 4097, 8191, 8192, 8193, 65535, 65536]
 DFS = [1, 2, 3, 10, 127, 129, 1000, 4094, 16382, 65534, 200000]
 # 400 per df: |t| over ten decades up to 60 (well beyond, at the larger df, p is so far below the doubles that mpmath's series
 # gives up), and evenly from 0 (p = 1) to 45, where p has left the doubles at the larger df
 TS = np.concatenate([np.geomspace(1e-8, 60.0, 200), np.linspace(0.0, 45.0, 200)])
-
-
-def _host_compiler():
-    for name in (os.environ.get("CXX"), "c++", "g++", "clang++"):
-        if name and shutil.which(name):
-            return shutil.which(name)
-    return None
 
 
 def _p_mp(df, t):
@@ -41,9 +30,6 @@ def _p_mp(df, t):
 
 @pytest.fixture(scope="module")
 def host_run(tmp_path_factory):
-    cxx = _host_compiler()
-    if cxx is None:
-        pytest.skip("no host C++ compiler (c++, g++, clang++ or $CXX) on PATH")
     tmp = tmp_path_factory.mktemp("ttest_host")
     rng = np.random.RandomState(65536)
     blob = [struct.pack("=q", 2 * len(SIZES))]
@@ -58,11 +44,7 @@ def host_run(tmp_path_factory):
     blob += [struct.pack("=q", len(pairs)), pairs.tobytes()]
     data = tmp / "vectors.bin"
     data.write_bytes(b"".join(blob))
-    exe = tmp / "ttest_host_check"
-    subprocess.check_call([cxx, "-std=c++17", "-O1", "-ffp-contract=off", "-Wall", "-Werror", "-I",
-                           os.path.join(ROOT, "subphaser_amd", "csrc"), "-o", str(exe),
-                           os.path.join(ROOT, "tests", "ttest_host_check.cpp"), "-lm"])
-    r = subprocess.run([str(exe), str(data)], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=300)
+    r = host_check.run(tmp, "ttest_host_check", [data], flags=["-ffp-contract=off"], libs=["-lm"])
     return r, pairs
 
 
