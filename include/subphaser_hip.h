@@ -250,6 +250,27 @@ int sp_kmer_ttest(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const i
 int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
                        const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                        double *pvals, double *means);
+/* The same stage for test_method = kruskal (method 0) and mannwhitneyu (method 1), Cluster.py:178-194: arguments as in
+ * sp_kmer_ttest (`counts` a host or a device pointer: rows staged on this device are read in place), and means, top and
+ * second are formed exactly as sp_kmer_ttest forms them, so one matrix gets the same pair of groups under every method.
+ * The test runs between the values of the top group and those of the second; csrc/sp_ranktest.h states the arithmetic:
+ * doubled midranks by counting comparisons (integers), the rank sums and the tie term from them, and
+ *   kruskal       H with scipy's tie correction in scipy's order of operations, p = erfc(sqrt(H / 2)); all values
+ *                 identical: p = 1, stat = NaN (scipy raises there and the reference's caller never sees a value);
+ *   mannwhitneyu  scipy 1.15's two-sided test, use_continuity=True, method="auto": the exact null distribution (tables
+ *                 built on the host per size pair in integers and uploaded with the call) when a row has no ties and one
+ *                 of the two groups has at most 8 chromosomes, the normal approximation with the tie correction
+ *                 otherwise; p clipped to [0, 1].
+ * stat: M statistics (H, or U of the top group) -- bit-defined; may be NULL.  pvals differ from scipy's only through erfc.
+ * One group alone: second = top, p = 1, stat = NaN.  k7_ranktest is one thread per row with the pooled values in LDS;
+ * every loop is bounded by the 128 values a row can have.
+ * SP_EINVAL: a NULL pointer, method outside 0..1, an empty group, a chromosome index outside [0, C), a length <= 0.
+ * SP_EUNSUP: a group of more than 64 chromosomes (decided before any allocation).  SP_ENOMEM: the workspace does not fit
+ * (the message carries its size).  M == 0: SP_OK without a launch.                                                  */
+int sp_kmer_ranktest(sp_ctx *ctx, const uint32_t *counts /*host or device*/, int64_t M, int C, const int64_t *lengths,
+                     int n_groups, const int32_t *group_off, const int32_t *group_chrom,
+                     int method /*0 kruskal, 1 mannwhitneyu*/, int32_t *top, int32_t *second, double *pvals,
+                     double *means /*M x n_groups*/, double *stat /*M, or NULL*/);
 
 /* ---- bootstrap support of the chromosome -> subgenome assignment -----------------------------
  * Replaces the loop of Cluster.bootstrap (Cluster.py:82-118): R k-means fits, replicate r on the n columns

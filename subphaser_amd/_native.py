@@ -18,6 +18,8 @@ SP_OK, SP_EINVAL, SP_EUNSUP, SP_ENOMEM, SP_EHIP, SP_ENODEV, SP_ESTATE, SP_EIO = 
 KBOOT_MAX_POINTS, KBOOT_MAX_CLUSTERS = 128, 32     # SP_KB_MAXC, SP_KB_MAXK in csrc/sp_kboot.h
 KPCA_MAX_CHROM, KPCA_MAX_COMP = 1024, 32           # SP_KP_MAXC, SP_KP_MAXCOMP in csrc/sp_kpca.h
 HCLUST_MAX_POINTS = 16384                          # SP_HC_MAXP in csrc/sp_hclust.h
+RANKTEST_MAX_GROUP = 64                            # SP_RT_MAXG in csrc/sp_ranktest.h
+RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: the `method` argument is the index
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -26,7 +28,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -115,6 +117,7 @@ def load():
     L.sp_enrich_dev.argtypes = [vp, vp, i64, ci, dbl, dbl, vp, vp, vp, vp]
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
+    L.sp_kmer_ranktest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
     L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
     L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
     L.sp_kmer_pca_signs.argtypes = [vp, vp, i64, ci, vp, vp, ci, vp, vp]
@@ -770,6 +773,13 @@ class Context:
         left-to-right sum over the list divided by its length (Cluster.py:181-183)."""
         return self._kmer_ttest(self.L.sp_kmer_ttest_wide, counts, lengths, groups)
 
+    @staticmethod
+    def _groups_arg(groups):
+        """group_off int32 [n_groups + 1], group_chrom int32: the chromosome lists back to back"""
+        goff = np.zeros(len(groups) + 1, np.int32)
+        goff[1:] = np.cumsum([len(g) for g in groups])
+        return goff, np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups]), np.int32)
+
     def _kmer_ttest(self, entry, counts, lengths, groups):
         if isinstance(counts, tuple):
             d_ptr, M, Cn = counts
@@ -779,14 +789,34 @@ class Context:
             M, Cn = counts.shape
             cptr = _p(counts)
         lengths = np.ascontiguousarray(lengths, np.int64)
-        goff = np.zeros(len(groups) + 1, np.int32)
-        goff[1:] = np.cumsum([len(g) for g in groups])
-        gch = np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups]), np.int32)
+        goff, gch = self._groups_arg(groups)
         top, second = np.empty(M, np.int32), np.empty(M, np.int32)
         pvals, means = np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
         self._ck(entry(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
                        _p(top), _p(second), _p(pvals), _p(means)))
         return top, second, pvals, means
+
+    def kmer_ranktest(self, counts, lengths, groups, method):
+        """Cluster.output_kmers' per-k-mer test for test_method "kruskal" or "mannwhitneyu" on the device
+        (sp_kmer_ranktest; `method` is the name, or its index in RANKTEST_METHODS).  counts, lengths and groups as in
+        kmer_ttest -- counts may be (device pointer, M, C) from stage_rows -- with at most RANKTEST_MAX_GROUP chromosomes
+        per group (ValueError beyond).  Returns (top, second, pvals, means [M, n_groups], stat): means, top and second as
+        kmer_ttest gives them, stat the statistic (H, or U of the top group; NaN where the test has none), bit-defined
+        by csrc/sp_ranktest.h."""
+        if isinstance(method, str):
+            if method not in RANKTEST_METHODS:
+                raise ValueError("method must be one of {}".format(RANKTEST_METHODS))
+            method = RANKTEST_METHODS.index(method)
+        keep, cptr, M, Cn = self._rows_arg(counts)
+        lengths = np.ascontiguousarray(lengths, np.int64)
+        if lengths.shape != (Cn,):
+            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
+        goff, gch = self._groups_arg(groups)
+        top, second = np.empty(M, np.int32), np.empty(M, np.int32)
+        pvals, stat, means = np.empty(M, np.float64), np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
+        self._ck(self.L.sp_kmer_ranktest(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch), int(method),
+                                         _p(top), _p(second), _p(pvals), _p(means), _p(stat)))
+        return top, second, pvals, means, stat
 
     def kmeans_bootstrap(self, z, cols, K, seed, want_gram=False):
         """Cluster.bootstrap's k-means fits on the device (sp_kmeans_bootstrap): replicate r clusters the C rows of z

@@ -355,7 +355,7 @@ class Cluster:
             fout.write("{}\t{}\t{}\n".format(c, self.d_sg[c], self.d_bs[c]))
 
     def output_kmers(self, fout=sys.stdout, max_pval=0.05, ncpu=4, method="map", test_method="ttest_ind", defer=False):
-        """Student t-test (pooled variance, two-sided) between the highest-mean and the
+        """Student t-test (pooled variance, two-sided; or the `test_method` given) between the highest-mean and the
         second-highest-mean subgenome groups of every k-mer; keeps p <= max_pval.
         Returns KmerLabels (array form of the reference's d_ksg dict).
         defer=True: nothing is written; returns (KmerLabels, write) where write(fout) produces the same text later
@@ -379,6 +379,17 @@ class Cluster:
             elif biggest <= TTEST_WIDE_MAX_GROUP:
                 entry = getattr(ctx, "kmer_ttest_wide", None)
         staged = getattr(self, "_counts_dev", None)      # rows already on the device (the CLI stages them early)
+        if test_method in _native.RANKTEST_METHODS:
+            # the two rank-sum tests: k7_ranktest (csrc/sp_ranktest.hip) ranks the two chosen groups in LDS, up to
+            # RANKTEST_MAX_GROUP chromosomes each; the numpy / scipy code below otherwise
+            rank_entry = self._device_ranktest(ctx, M, biggest, test_method)
+            if rank_entry is not None:
+                try:
+                    top, second, pvals, means, _ = rank_entry(staged if staged else self._counts, self._lengths, groups,
+                                                              test_method)
+                finally:
+                    self._release_staged(ctx, staged)
+                return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
         if entry is not None:
             # device path: a thread per k-mer (csrc/sp_enrich.hip); the numpy code below is the same test for matrices
             # that only exist as a `.kmer.mat` file or behind a context without the kernel
@@ -390,6 +401,22 @@ class Cluster:
         self._release_staged(ctx, staged)               # the numpy code reads the host matrix
         top, second, pvals, means = numpy_kmer_test(X, groups, test_method)
         return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
+
+    def _device_ranktest(self, ctx, M, biggest, test_method):
+        """Context.kmer_ranktest when the device engine applies, else None (one log line says why)"""
+        entry = getattr(ctx, "kmer_ranktest", None)
+        if entry is None:
+            why = "no device context with the rank-sum tests"
+        elif getattr(self, "_counts", None) is None or self._lengths is None:
+            why = "the matrix has no integer counts and lengths"
+        elif not M:
+            why = "no k-mers"
+        elif biggest > _native.RANKTEST_MAX_GROUP:
+            why = "a subgenome of {} chromosomes (the device engine takes up to {})".format(biggest, _native.RANKTEST_MAX_GROUP)
+        else:
+            return entry
+        logger.info("k-mer test ({}) on the host: {}".format(test_method, why))
+        return None
 
     def _release_staged(self, ctx, staged):
         if staged and hasattr(ctx, "release_rows"):
