@@ -2,6 +2,7 @@
 // filter, the pair-table field layout, the output-slot arithmetic of Seqs.map_kmer3's chunks and bins.
 #pragma once
 #include "sp_device.h"
+#include "sp_maphash.h"
 
 #ifndef MAP_BLOOM_MAX_BITS
 #define MAP_BLOOM_MAX_BITS 25
@@ -27,8 +28,9 @@
 // at 4 MiB the filter falls out of the L2 and the gain is gone: profiles/r06_notes.md, section 3.)  The minimum of two uniform
 // hashes is not uniform (density 2 (1 - u)); 1 - (1 - u)^2 is, and that is what indexes the words, so the fill stays even.
 // The three bits inside the word still come from the hashed (k-1)-mer.  k < 5 (cores of fewer than two bases): the old addressing.
-#define MAP_BLOOM_CORE 0x100          // flag in the `nbits` argument of everything below (ctx->bloom_bits carries it)
-#define MAP_BLOOM_NBITS(nb) ((nb) & 0xFF)
+// (MAP_BLOOM_CORE, the flag in the `nbits` argument of everything below, and the hash functions themselves: sp_maphash.h.
+// That is the family of k > 15; at k <= 15 the mirror image -- the LARGER hash and u^2 -- addresses the word and the three
+// bits come from the two core hashes: the same design on cheaper arithmetic, profiles/map_hash_notes.md.)
 // Runs (profiles/map_runs_notes.md).  Labelled k-mers come in runs -- inside a repeat copy every quad of a lane is a candidate --
 // and a candidate quad goes to the exact table whatever the filter says, so the two-phase walk of k <= 15 (map_unit_scan64)
 // does not ASK the filter inside a run: a lane whose last MAP_RUNS_R probed quads passed on both pairs enqueues the next quad
@@ -43,44 +45,6 @@
 #ifndef MAP_RUNS_P
 #define MAP_RUNS_P 3
 #endif
-struct map_bloom_probe {
-    uint32_t word, bits;
-};
-__host__ __device__ __forceinline__ uint32_t map_core_hash(uint64_t t) {       // of a canonical (k-3)-mer; well mixed in its HIGH bits
-    uint32_t x = (uint32_t)t ^ (uint32_t)(t >> 32);
-    x *= 0x9E3779B1u;
-    x ^= x >> 15;
-    return x * 0x85EBCA6Bu;      // (multiply - xorshift - multiply: the scan computes one of these per pair)
-}
-__host__ __device__ __forceinline__ uint32_t map_core_word(uint32_t hmin /* the smaller of a (k-1)-mer's two core hashes */, int nbits) {
-    const uint32_t n = ~hmin;
-    const uint32_t sq = (uint32_t)(((unsigned long long)n * (unsigned long long)n) >> 32);      // (1 - u)^2
-    return (~sq) >> (32 - (MAP_BLOOM_NBITS(nbits) - 5));
-}
-__host__ __device__ __forceinline__ uint32_t map_bloom_bits3(uint64_t x64, uint32_t &h) {      // the three bits of a canonical (k-1)-mer
-    const uint32_t x = (uint32_t)x64 ^ (uint32_t)(x64 >> 32);
-    h = x * 0x9E3779B1u;
-    const uint32_t h2 = x * 0x85EBCA6Bu;
-    return (1u << ((h >> 7) & 31u)) | (1u << ((h >> 2) & 31u)) | (1u << (h2 >> 27));
-}
-// word + bits of the CANONICAL (k-1)-mer x64 of a k-mer pair (generic form: the filter build and the rolling scans; the rolled
-// scans of sp_map.hip / sp_sparse.hip compute the same from the windows they already hold)
-__host__ __device__ __forceinline__ map_bloom_probe map_bloom(uint64_t x64, int k, int nbits) {
-    map_bloom_probe p;
-    uint32_t h;
-    p.bits = map_bloom_bits3(x64, h);
-    if (!(nbits & MAP_BLOOM_CORE) || k < 5) {
-        p.word = h >> (32 - (MAP_BLOOM_NBITS(nbits) - 5));
-        return p;
-    }
-    const int cb = 2 * (k - 3);
-    const uint64_t smask = (1ULL << cb) - 1ULL;
-    const uint64_t a = x64 >> 4, b = x64 & smask;               // first / last k-3 bases
-    const uint64_t ar = sp_revcomp(a, k - 3), br = sp_revcomp(b, k - 3);
-    const uint32_t ha = map_core_hash(a < ar ? a : ar), hb = map_core_hash(b < br ? b : br);
-    p.word = map_core_word(ha < hb ? ha : hb, nbits);
-    return p;
-}
 __device__ __forceinline__ bool map_bloom_test(const uint32_t *__restrict__ bloom, int nbits, int k, uint64_t x) {
     const map_bloom_probe p = map_bloom(x, k, nbits);
     return (bloom[p.word] & p.bits) == p.bits;
@@ -162,20 +126,12 @@ struct map_ptab {
     uint32_t ovf_mask;                // its size - 1
     int sb, tb;                       // bits of the shared (k-3)-mer 2(k-3), bits of mix(t) kept in the tag
 };
-__host__ __device__ __forceinline__ uint32_t map_ct_mix(uint32_t x, int kb) {
-    const uint32_t m = kb >= 32 ? 0xFFFFFFFFu : ((1u << kb) - 1u);
-    uint32_t h = (x * 0x9E3779B1u) & m;        // odd multiplier: a bijection of the kb-bit values
-    h ^= h >> ((kb + 1) / 2);                  // xorshift by at least half the width: an involution-like bijection
-    h = (h * 0x85EBCA6Bu) & m;
-    h ^= h >> ((kb + 1) / 2);
-    return h;
-}
 __host__ __device__ __forceinline__ uint32_t map_ct_ovf_home(uint32_t x) { return (x * 0xC2B2AE35u) >> 7; }
 struct map_ct_key {
     uint32_t bucket, tag, kid;        // kid: (t, side, e) packed, the overflow table's key
 };
 __host__ __device__ __forceinline__ map_ct_key map_ct_key_of(const map_ptab &T, uint32_t t, uint32_t side, uint32_t e) {
-    const uint32_t h = map_ct_mix(t, T.sb);
+    const uint32_t h = map_ct_mix24(t, T.sb);      // (a map_ptab exists at k <= 15 only: sb <= 24 -- sp_maphash.h)
     map_ct_key r;
     r.bucket = h >> T.tb;
     r.tag = ((h & ((1u << T.tb) - 1u)) << 5) | (side << 4) | e;

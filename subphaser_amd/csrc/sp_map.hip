@@ -309,7 +309,13 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
     const uint32_t cmask = kp.k >= 5 ? ((1u << (2 * (kp.k - 3))) - 1u) : 0u;
     const int wsh = 32 - (MAP_BLOOM_NBITS(nbits) - 5);
     uint32_t last_wi = 0xFFFFFFFFu, last_w = 0u;                  // the word this lane fetched last (index, content)
-    uint32_t h_carry = 0u;                                         // hash of the core the previous quad ended with
+    // hash of the core the previous quad ended with, which is the core the next one begins with; the unit's first quad has
+    // no predecessor: its first core is hashed here, once, and not behind a test in the loop
+    uint32_t h_carry = 0u;
+    if (core) {
+        const map_quad_win Q0 = map_quad_windows(l0, l1, m0, m1, 0, sh, m1mask);
+        h_carry = map_chain_start24(Q0.xf1, Q0.xr1, cmask);
+    }
     // runs (sp_map.h), one counter per lane: below MAP_RUNS_R it is the lane's probed quads that passed on both pairs, in a
     // row; from there on, MAP_RUNS_R + the quads it has predicted since.  Per unit: 0 here, carried over the rounds.
     static_assert(MAP2_QI == 1, "the runs rule decides a quad from the filter's answer for the quad before it");
@@ -332,29 +338,19 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
                 for (int q = 0; q < MAP2_QI; q++) {
                     const int r = r0 + 4 * q, j = 16 * w + r;     // the quad's first start; its pairs share x1 (at j + 1) and x2 (at j + 3)
                     const map_quad_win Q = map_quad_windows(l0, l1, m0, m1, r, sh, m1mask);
-                    const uint32_t c1 = Q.xf1 < Q.xr1 ? Q.xf1 : Q.xr1, c2 = Q.xf2 < Q.xr2 ? Q.xf2 : Q.xr2;
-                    uint32_t h1, h2;
-                    bt1[q] = map_bloom_bits3((uint64_t)c1, h1);
-                    bt2[q] = map_bloom_bits3((uint64_t)c2, h2);
                     const uint32_t okx = (uint32_t)(ok_x >> j);
                     v1[q] = okx & 1u;
                     v2[q] = okx & 4u;
+                    // word and bits of x1 and x2: the 24-bit family of sp_maphash.h (k <= 15 here: no choice per quad)
                     if (core) {
-                        // the chain of cores: a = first k-3 bases of x1, b = last of x1 = first of x2, c = last of x2 (= the next
-                        // quad's a); canonical = the smaller of the forward reading and its reverse complement, which is the
-                        // OTHER end of the reverse-complemented (k-1)-mer
-                        const uint32_t tb_f = Q.xf1 & cmask, tb_r = Q.xr1 >> 4, tc_f = Q.xf2 & cmask, tc_r = Q.xr2 >> 4;
-                        uint32_t ha = h_carry;              // (this quad's a IS the previous quad's c: the same bases)
-                        if (j == 0) {                       // (uniform: the unit's first quad)
-                            const uint32_t ta_f = Q.xf1 >> 4, ta_r = Q.xr1 & cmask;
-                            ha = map_core_hash((uint64_t)(ta_f < ta_r ? ta_f : ta_r));
-                        }
-                        const uint32_t hb = map_core_hash((uint64_t)(tb_f < tb_r ? tb_f : tb_r));
-                        const uint32_t hc = map_core_hash((uint64_t)(tc_f < tc_r ? tc_f : tc_r));
-                        h_carry = hc;
-                        wi1[q] = map_core_word(ha < hb ? ha : hb, nbits);
-                        wi2[q] = map_core_word(hb < hc ? hb : hc, nbits);
+                        map_bloom_probe p1, p2;
+                        map_quad_probes24(Q.xf1, Q.xr1, Q.xf2, Q.xr2, cmask, nbits, h_carry, p1, p2);
+                        wi1[q] = p1.word; bt1[q] = p1.bits;
+                        wi2[q] = p2.word; bt2[q] = p2.bits;
                     } else {
+                        uint32_t h1, h2;
+                        bt1[q] = map_bloom_bits3_24(Q.xf1 < Q.xr1 ? Q.xf1 : Q.xr1, h1);
+                        bt2[q] = map_bloom_bits3_24(Q.xf2 < Q.xr2 ? Q.xf2 : Q.xr2, h2);
                         wi1[q] = h1 >> wsh;
                         wi2[q] = h2 >> wsh;
                     }
