@@ -271,6 +271,29 @@ int sp_kmer_ranktest(sp_ctx *ctx, const uint32_t *counts /*host or device*/, int
                      int n_groups, const int32_t *group_off, const int32_t *group_chrom,
                      int method /*0 kruskal, 1 mannwhitneyu*/, int32_t *top, int32_t *second, double *pvals,
                      double *means /*M x n_groups*/, double *stat /*M, or NULL*/);
+/* The same stage for test_method = wilcoxon, Cluster.py:178-194: arguments as in sp_kmer_ranktest without `method`
+ * (`counts` a host or a device pointer: rows staged on this device are read in place); means, top and second are formed
+ * exactly as sp_kmer_ttest and sp_kmer_ranktest form them.  The test is paired: every group has the same number n of
+ * chromosomes, 2 <= n <= 64, and pair j is (j-th chromosome of the top group, j-th of the second), both in list order.
+ * csrc/sp_wilcoxon.h states the arithmetic -- d = a - b on the fp64 quotients count / length, zeros dropped, doubled
+ * midranks of the nonzero |d| by counting comparisons (integers), stat = min(r_plus, r_minus) -- and the branch scipy
+ * 1.13 .. 1.16 takes per row under method="auto", correction=False:
+ *   exact        no zero, no tie, n <= 50: the null distribution of r_plus (one table for n, built on the host in
+ *                integers and uploaded with the call);
+ *   permutation  a zero or a tie, n <= 13: all 2^n sign assignments, counted in integers by a Gray-code walk -- p is
+ *                bit-defined and equal to scipy's; all d zero: p = 1;
+ *   asymptotic   otherwise: the normal approximation with the tie correction; all d zero: p = NaN, as scipy returns
+ *                (the caller keeps NaN rows).
+ * stat: M statistics -- bit-defined; may be NULL.  The exact and the asymptotic p differ from scipy's only in the last bits.
+ * One group alone: second = top, p = 1, stat = NaN.  k7_wilcoxon is one thread per row with the pairs in LDS; every loop
+ * is bounded by n^2 or by 2^13.
+ * SP_EINVAL: a NULL pointer, an empty group, a chromosome index outside [0, C), a length <= 0.
+ * SP_EUNSUP: groups that do not all have one size, a size of 1, a size above 64 (decided before any allocation; the
+ * message carries the sizes).  SP_ENOMEM: the workspace does not fit (the message carries its size).  M == 0: SP_OK
+ * without a launch.                                                                                                  */
+int sp_kmer_wilcoxon(sp_ctx *ctx, const uint32_t *counts /*host or device*/, int64_t M, int C, const int64_t *lengths,
+                     int n_groups, const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
+                     double *pvals, double *means /*M x n_groups*/, double *stat /*M, or NULL*/);
 
 /* ---- bootstrap support of the chromosome -> subgenome assignment -----------------------------
  * Replaces the loop of Cluster.bootstrap (Cluster.py:82-118): R k-means fits, replicate r on the n columns

@@ -20,6 +20,7 @@ KPCA_MAX_CHROM, KPCA_MAX_COMP = 1024, 32           # SP_KP_MAXC, SP_KP_MAXCOMP i
 HCLUST_MAX_POINTS = 16384                          # SP_HC_MAXP in csrc/sp_hclust.h
 RANKTEST_MAX_GROUP = 64                            # SP_RT_MAXG in csrc/sp_ranktest.h
 RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: the `method` argument is the index
+WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
 SYMBOLS = [
@@ -28,7 +29,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -118,6 +119,7 @@ def load():
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ranktest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.sp_kmer_wilcoxon.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
     L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
     L.sp_kmer_pca_signs.argtypes = [vp, vp, i64, ci, vp, vp, ci, vp, vp]
@@ -815,6 +817,24 @@ class Context:
         top, second = np.empty(M, np.int32), np.empty(M, np.int32)
         pvals, stat, means = np.empty(M, np.float64), np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
         self._ck(self.L.sp_kmer_ranktest(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch), int(method),
+                                         _p(top), _p(second), _p(pvals), _p(means), _p(stat)))
+        return top, second, pvals, means, stat
+
+    def kmer_wilcoxon(self, counts, lengths, groups):
+        """Cluster.output_kmers' per-k-mer test for test_method "wilcoxon" on the device (sp_kmer_wilcoxon).  counts,
+        lengths and groups as in kmer_ranktest -- counts may be (device pointer, M, C) from stage_rows.  The test is
+        paired: every group has the same number of chromosomes, 2 .. WILCOXON_MAX_GROUP (ValueError otherwise).  Returns
+        (top, second, pvals, means [M, n_groups], stat): means, top and second as kmer_ttest gives them, stat
+        min(r_plus, r_minus) (NaN for a single group), bit-defined by csrc/sp_wilcoxon.h; p is NaN where scipy's is (all
+        differences zero at more than 13 pairs)."""
+        keep, cptr, M, Cn = self._rows_arg(counts)
+        lengths = np.ascontiguousarray(lengths, np.int64)
+        if lengths.shape != (Cn,):
+            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
+        goff, gch = self._groups_arg(groups)
+        top, second = np.empty(M, np.int32), np.empty(M, np.int32)
+        pvals, stat, means = np.empty(M, np.float64), np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
+        self._ck(self.L.sp_kmer_wilcoxon(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
                                          _p(top), _p(second), _p(pvals), _p(means), _p(stat)))
         return top, second, pvals, means, stat
 

@@ -390,6 +390,16 @@ class Cluster:
                 finally:
                     self._release_staged(ctx, staged)
                 return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
+        if test_method == "wilcoxon":
+            # the paired test: k7_wilcoxon (csrc/sp_wilcoxon.hip) when every subgenome has the same number of chromosomes,
+            # 2 .. WILCOXON_MAX_GROUP; the numpy / scipy code below otherwise (unequal sizes: scipy raises there)
+            wx_entry = self._device_wilcoxon(ctx, M, groups)
+            if wx_entry is not None:
+                try:
+                    top, second, pvals, means, _ = wx_entry(staged if staged else self._counts, self._lengths, groups)
+                finally:
+                    self._release_staged(ctx, staged)
+                return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
         if entry is not None:
             # device path: a thread per k-mer (csrc/sp_enrich.hip); the numpy code below is the same test for matrices
             # that only exist as a `.kmer.mat` file or behind a context without the kernel
@@ -416,6 +426,26 @@ class Cluster:
         else:
             return entry
         logger.info("k-mer test ({}) on the host: {}".format(test_method, why))
+        return None
+
+    def _device_wilcoxon(self, ctx, M, groups):
+        """Context.kmer_wilcoxon when the device engine applies, else None (one log line says why; a context without
+        the entry is silent)"""
+        entry = getattr(ctx, "kmer_wilcoxon", None)
+        if entry is None:
+            return None
+        sizes = sorted({len(g) for g in groups})
+        if getattr(self, "_counts", None) is None or self._lengths is None:
+            why = "the matrix has no integer counts and lengths"
+        elif not M:
+            why = "no k-mers"
+        elif len(sizes) > 1:
+            why = "subgenomes of {} chromosomes (the paired test needs one size)".format(", ".join(map(str, sizes)))
+        elif sizes[0] < 2 or sizes[0] > _native.WILCOXON_MAX_GROUP:
+            why = "subgenomes of {} chromosomes (the device engine takes 2 to {})".format(sizes[0], _native.WILCOXON_MAX_GROUP)
+        else:
+            return entry
+        logger.info("k-mer test (wilcoxon) on the host: {}".format(why))
         return None
 
     def _release_staged(self, ctx, staged):

@@ -200,7 +200,7 @@ struct sp_ctx {
     int64_t sf_n = 0;
     uint64_t *d_hkeys = nullptr;   // open-addressing hash table of the labelled k-mers: 16-B entries {key, label}
     int64_t hcap = 0;
-    sp_buf b_tt;            // k-mer test workspace: the t-tests (sp_enrich.hip) and the rank-sum tests (sp_ranktest.hip)
+    sp_buf b_tt;            // k-mer test workspace: the t-tests (sp_enrich.hip), the rank-sum tests (sp_ranktest.hip), the paired test (sp_wilcoxon.hip)
     sp_buf b_kb;            // k-means bootstrap: columns, labels, iteration counts, Gram copies (sp_kboot.hip)
     sp_buf b_kp;            // k-mer PCA: lengths, row statistics, chunk partials, sign candidates (sp_kpca.hip)
     sp_buf b_hc;            // heatmap clustering: points, the P x P distance matrix, merges, chain state (sp_hclust.hip)
