@@ -767,13 +767,13 @@ class Context:
         filter_fetch returns them), lengths: int64 [C], groups: list of chromosome-index lists in sorted
         subgenome-name order.  Returns (top, second, pvals, means [M, n_groups]).
         counts may also be (device pointer, M, C): rows staged on the device earlier (stage_rows)."""
-        return self._kmer_ttest(self.L.sp_kmer_ttest, counts, lengths, groups)
+        return self._kmer_test(self.L.sp_kmer_ttest, counts, lengths, groups)
 
     def kmer_ttest_wide(self, counts, lengths, groups):
         """kmer_ttest for subgenomes of up to 65536 chromosomes (sp_kmer_ttest_wide): same arguments and results.
         means are np.mean of a group's list (pairwise), top / second follow the reference's order key, the
         left-to-right sum over the list divided by its length (Cluster.py:181-183)."""
-        return self._kmer_ttest(self.L.sp_kmer_ttest_wide, counts, lengths, groups)
+        return self._kmer_test(self.L.sp_kmer_ttest_wide, counts, lengths, groups)
 
     @staticmethod
     def _groups_arg(groups):
@@ -782,21 +782,19 @@ class Context:
         goff[1:] = np.cumsum([len(g) for g in groups])
         return goff, np.ascontiguousarray(np.concatenate([np.asarray(g, np.int32) for g in groups]), np.int32)
 
-    def _kmer_ttest(self, entry, counts, lengths, groups):
-        if isinstance(counts, tuple):
-            d_ptr, M, Cn = counts
-            cptr = C.c_void_p(int(d_ptr))
-        else:
-            counts = np.ascontiguousarray(counts, np.uint32)
-            M, Cn = counts.shape
-            cptr = _p(counts)
+    def _kmer_test(self, entry, counts, lengths, groups, extra=(), want_stat=False):
+        """One call of a k-mer test entry: `extra` are its arguments between the group lists and the results, the
+        statistic follows the means with want_stat.  Returns (top, second, pvals, means[, stat])."""
+        keep, cptr, M, Cn = self._rows_arg(counts)      # `keep` and the arrays below stay alive across the call
         lengths = np.ascontiguousarray(lengths, np.int64)
+        if lengths.shape != (Cn,):
+            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
         goff, gch = self._groups_arg(groups)
         top, second = np.empty(M, np.int32), np.empty(M, np.int32)
         pvals, means = np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
-        self._ck(entry(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
-                       _p(top), _p(second), _p(pvals), _p(means)))
-        return top, second, pvals, means
+        out = (top, second, pvals, means) + ((np.empty(M, np.float64),) if want_stat else ())
+        self._ck(entry(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch), *extra, *map(_p, out)))
+        return out
 
     def kmer_ranktest(self, counts, lengths, groups, method):
         """Cluster.output_kmers' per-k-mer test for test_method "kruskal" or "mannwhitneyu" on the device
@@ -809,16 +807,7 @@ class Context:
             if method not in RANKTEST_METHODS:
                 raise ValueError("method must be one of {}".format(RANKTEST_METHODS))
             method = RANKTEST_METHODS.index(method)
-        keep, cptr, M, Cn = self._rows_arg(counts)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        if lengths.shape != (Cn,):
-            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
-        goff, gch = self._groups_arg(groups)
-        top, second = np.empty(M, np.int32), np.empty(M, np.int32)
-        pvals, stat, means = np.empty(M, np.float64), np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
-        self._ck(self.L.sp_kmer_ranktest(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch), int(method),
-                                         _p(top), _p(second), _p(pvals), _p(means), _p(stat)))
-        return top, second, pvals, means, stat
+        return self._kmer_test(self.L.sp_kmer_ranktest, counts, lengths, groups, extra=(int(method),), want_stat=True)
 
     def kmer_wilcoxon(self, counts, lengths, groups):
         """Cluster.output_kmers' per-k-mer test for test_method "wilcoxon" on the device (sp_kmer_wilcoxon).  counts,
@@ -827,16 +816,7 @@ class Context:
         (top, second, pvals, means [M, n_groups], stat): means, top and second as kmer_ttest gives them, stat
         min(r_plus, r_minus) (NaN for a single group), bit-defined by csrc/sp_wilcoxon.h; p is NaN where scipy's is (all
         differences zero at more than 13 pairs)."""
-        keep, cptr, M, Cn = self._rows_arg(counts)
-        lengths = np.ascontiguousarray(lengths, np.int64)
-        if lengths.shape != (Cn,):
-            raise ValueError("{} lengths for {} chromosomes".format(lengths.size, Cn))
-        goff, gch = self._groups_arg(groups)
-        top, second = np.empty(M, np.int32), np.empty(M, np.int32)
-        pvals, stat, means = np.empty(M, np.float64), np.empty(M, np.float64), np.empty((M, len(groups)), np.float64)
-        self._ck(self.L.sp_kmer_wilcoxon(self.h, cptr, M, Cn, _p(lengths), len(groups), _p(goff), _p(gch),
-                                         _p(top), _p(second), _p(pvals), _p(means), _p(stat)))
-        return top, second, pvals, means, stat
+        return self._kmer_test(self.L.sp_kmer_wilcoxon, counts, lengths, groups, want_stat=True)
 
     def kmeans_bootstrap(self, z, cols, K, seed, want_gram=False):
         """Cluster.bootstrap's k-means fits on the device (sp_kmeans_bootstrap): replicate r clusters the C rows of z

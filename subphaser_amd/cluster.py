@@ -367,86 +367,41 @@ class Cluster:
         X = self.raw_data
         M = X.shape[0]
         ctx = getattr(self, "_ctx", None)
-        # k7_ttest keeps a group's values in registers: at most TTEST_MAX_GROUP chromosomes per subgenome (sp_kmer_ttest
-        # returns SP_EUNSUP beyond).  Scaffold-level runs with larger groups, up to TTEST_WIDE_MAX_GROUP, take
-        # k7_ttest_wide* (sp_kmer_ttest_wide) when the context has it, the numpy code below otherwise.
-        biggest = max(len(g) for g in groups)
-        entry = None
-        if (test_method == "ttest_ind" and M and ctx is not None
-                and getattr(self, "_counts", None) is not None and self._lengths is not None):
-            if biggest <= TTEST_MAX_GROUP:
-                entry = getattr(ctx, "kmer_ttest", None)
-            elif biggest <= TTEST_WIDE_MAX_GROUP:
-                entry = getattr(ctx, "kmer_ttest_wide", None)
         staged = getattr(self, "_counts_dev", None)      # rows already on the device (the CLI stages them early)
-        if test_method in _native.RANKTEST_METHODS:
-            # the two rank-sum tests: k7_ranktest (csrc/sp_ranktest.hip) ranks the two chosen groups in LDS, up to
-            # RANKTEST_MAX_GROUP chromosomes each; the numpy / scipy code below otherwise
-            rank_entry = self._device_ranktest(ctx, M, biggest, test_method)
-            if rank_entry is not None:
-                try:
-                    top, second, pvals, means, _ = rank_entry(staged if staged else self._counts, self._lengths, groups,
-                                                              test_method)
-                finally:
-                    self._release_staged(ctx, staged)
-                return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
-        if test_method == "wilcoxon":
-            # the paired test: k7_wilcoxon (csrc/sp_wilcoxon.hip) when every subgenome has the same number of chromosomes,
-            # 2 .. WILCOXON_MAX_GROUP; the numpy / scipy code below otherwise (unequal sizes: scipy raises there)
-            wx_entry = self._device_wilcoxon(ctx, M, groups)
-            if wx_entry is not None:
-                try:
-                    top, second, pvals, means, _ = wx_entry(staged if staged else self._counts, self._lengths, groups)
-                finally:
-                    self._release_staged(ctx, staged)
-                return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
-        if entry is not None:
-            # device path: a thread per k-mer (csrc/sp_enrich.hip); the numpy code below is the same test for matrices
-            # that only exist as a `.kmer.mat` file or behind a context without the kernel
+        call, why = self._device_kmer_test(ctx, M, groups, test_method)
+        if why:
+            logger.info("k-mer test ({}) on the host: {}".format(test_method, why))
+        if call is None:
+            self._release_staged(ctx, staged)           # the numpy code reads the host matrix
+            top, second, pvals, means = numpy_kmer_test(X, groups, test_method)
+        else:
+            # device path: a thread per k-mer; the numpy code is the same test for matrices that only exist as a
+            # `.kmer.mat` file or behind a context without the kernel
             try:
-                top, second, pvals, means = entry(staged if staged else self._counts, self._lengths, groups)
+                top, second, pvals, means = call(staged if staged else self._counts, self._lengths, groups)[:4]
             finally:
                 self._release_staged(ctx, staged)       # M x C x 4 bytes of HBM nobody reads again
-            return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
-        self._release_staged(ctx, staged)               # the numpy code reads the host matrix
-        top, second, pvals, means = numpy_kmer_test(X, groups, test_method)
         return self._write_kmers(fout, sgs, top, pvals, means, max_pval, defer)
 
-    def _device_ranktest(self, ctx, M, biggest, test_method):
-        """Context.kmer_ranktest when the device engine applies, else None (one log line says why)"""
-        entry = getattr(ctx, "kmer_ranktest", None)
+    def _device_kmer_test(self, ctx, M, groups, test_method):
+        """(call, None) when a device engine of KMER_ENGINES applies -- call(rows, lengths, groups) returns (top, second,
+        pvals, means[, stat]) -- else (None, why): the reason for the log, None where the method stays silent"""
+        engines = KMER_ENGINES[test_method]
+        fits = [e for e in engines if e[2](groups) is None]
+        attr, extra, size_rule, says = fits[0] if fits else engines[-1]      # the first whose sizes fit
+        entry = getattr(ctx, attr, None)
         if entry is None:
-            why = "no device context with the rank-sum tests"
-        elif getattr(self, "_counts", None) is None or self._lengths is None:
-            why = "the matrix has no integer counts and lengths"
-        elif not M:
-            why = "no k-mers"
-        elif biggest > _native.RANKTEST_MAX_GROUP:
-            why = "a subgenome of {} chromosomes (the device engine takes up to {})".format(biggest, _native.RANKTEST_MAX_GROUP)
-        else:
-            return entry
-        logger.info("k-mer test ({}) on the host: {}".format(test_method, why))
-        return None
-
-    def _device_wilcoxon(self, ctx, M, groups):
-        """Context.kmer_wilcoxon when the device engine applies, else None (one log line says why; a context without
-        the entry is silent)"""
-        entry = getattr(ctx, "kmer_wilcoxon", None)
-        if entry is None:
-            return None
-        sizes = sorted({len(g) for g in groups})
+            why = says if isinstance(says, str) else None
+            return None, why
         if getattr(self, "_counts", None) is None or self._lengths is None:
             why = "the matrix has no integer counts and lengths"
         elif not M:
             why = "no k-mers"
-        elif len(sizes) > 1:
-            why = "subgenomes of {} chromosomes (the paired test needs one size)".format(", ".join(map(str, sizes)))
-        elif sizes[0] < 2 or sizes[0] > _native.WILCOXON_MAX_GROUP:
-            why = "subgenomes of {} chromosomes (the device engine takes 2 to {})".format(sizes[0], _native.WILCOXON_MAX_GROUP)
         else:
-            return entry
-        logger.info("k-mer test (wilcoxon) on the host: {}".format(why))
-        return None
+            why = size_rule(groups)
+        if why is None:
+            return (lambda rows, lengths, groups: entry(rows, lengths, groups, *extra)), None
+        return None, why if says else None
 
     def _release_staged(self, ctx, staged):
         if staged and hasattr(ctx, "release_rows"):
@@ -511,6 +466,40 @@ TEST_METHODS = ("ttest_ind", "kruskal", "wilcoxon", "mannwhitneyu")
 BOOTSTRAP_ENGINES = ("sklearn", "device")
 TTEST_MAX_GROUP = 64     # SP_TT_MAXG in csrc/sp_enrich.hip
 TTEST_WIDE_MAX_GROUP = 65536     # SP_TT_WIDE_MAX in csrc/sp_ttest.h
+
+
+def _groups_upto(limit):
+    def rule(groups):
+        biggest = max(len(g) for g in groups)
+        if biggest > limit():
+            return "a subgenome of {} chromosomes (the device engine takes up to {})".format(biggest, limit())
+    return rule
+
+
+def _wilcoxon_sizes(groups):
+    sizes = sorted({len(g) for g in groups})
+    if len(sizes) > 1:
+        return "subgenomes of {} chromosomes (the paired test needs one size)".format(", ".join(map(str, sizes)))
+    if sizes[0] < 2 or sizes[0] > _native.WILCOXON_MAX_GROUP:
+        return "subgenomes of {} chromosomes (the device engine takes 2 to {})".format(sizes[0], _native.WILCOXON_MAX_GROUP)
+
+
+# test_method -> its device engines, the first whose size rule passes is taken: (Context attribute, arguments behind the
+# group lists, size rule: groups -> None or why not, what the log says -- a string: every reason, this one for a context
+# without the entry; True: every reason but that one; False: nothing).
+#   ttest_ind     k7_ttest keeps a group's values in registers, up to TTEST_MAX_GROUP chromosomes (csrc/sp_enrich.hip);
+#                 scaffold-level runs with larger groups, up to TTEST_WIDE_MAX_GROUP, take k7_ttest_wide*
+#   rank-sum      k7_ranktest ranks the two chosen groups in LDS, up to RANKTEST_MAX_GROUP each (csrc/sp_ranktest.hip)
+#   wilcoxon      k7_wilcoxon: every subgenome has the same number of chromosomes, 2 .. WILCOXON_MAX_GROUP
+#                 (csrc/sp_wilcoxon.hip); unequal sizes reach scipy, which raises
+KMER_ENGINES = {
+    "ttest_ind": [("kmer_ttest", (), _groups_upto(lambda: TTEST_MAX_GROUP), False),
+                  ("kmer_ttest_wide", (), _groups_upto(lambda: TTEST_WIDE_MAX_GROUP), False)],
+    "wilcoxon": [("kmer_wilcoxon", (), _wilcoxon_sizes, True)],
+}
+for _m in _native.RANKTEST_METHODS:
+    KMER_ENGINES[_m] = [("kmer_ranktest", (_m,), _groups_upto(lambda: _native.RANKTEST_MAX_GROUP),
+                         "no device context with the rank-sum tests")]
 
 
 def numpy_kmer_test(X, groups, test_method="ttest_ind"):

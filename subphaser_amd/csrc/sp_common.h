@@ -222,6 +222,8 @@ int sp_scratch(sp_ctx *ctx, int64_t bytes, void **out);
 struct sp_ctx;
 int sp_buf_ensure(sp_ctx *ctx, sp_buf &b, int64_t bytes);
 void sp_buf_free(sp_buf &b);
+// does `p` point into this context's device memory (rows or a matrix staged earlier, read in place)?  Host pointers: false
+bool sp_on_device(sp_ctx *ctx, const void *p);
 void sp_prof_begin(sp_ctx *ctx, const char *name);
 void sp_prof_end(sp_ctx *ctx);
 void sp_prof_flush(sp_ctx *ctx);

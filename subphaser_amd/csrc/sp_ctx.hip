@@ -32,6 +32,13 @@ int sp_scratch(sp_ctx *ctx, int64_t bytes, void **out) {
     return SP_OK;
 }
 
+bool sp_on_device(sp_ctx *ctx, const void *p) {
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p) == hipSuccess) return at.type == hipMemoryTypeDevice && at.device == ctx->device;
+    (void)hipGetLastError();     // a plain malloc'ed pointer is "invalid value" for this query on some runtimes
+    return false;
+}
+
 int sp_buf_ensure(sp_ctx *ctx, sp_buf &b, int64_t bytes) {
     if (bytes <= b.cap) return SP_OK;
     if (b.p) {

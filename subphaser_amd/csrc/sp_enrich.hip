@@ -8,6 +8,7 @@
 // margins of 2e8 where a difference of lgamma() values loses 6-7 digits; the
 // tail is then summed by the exact term recurrence.  All arithmetic is fp64.
 #include "sp_device.h"
+#include "sp_kmertest.h"
 #include "sp_ttest.h"
 
 #define SP_MAX_INT_CLAMP (2147483647LL / 10)  // Stats.py:9
@@ -188,7 +189,8 @@ k6_enrich(const long long *__restrict__ counts, const long long *__restrict__ to
 // k-mer, the chromosome frequencies count/length are grouped by subgenome, the groups are ordered by mean
 // (descending, ties in subgenome order) and scipy.stats.ttest_ind(top, second) -- pooled variance, two-sided --
 // gives the p-value: 2 * stdtr(df, -|t|) = I_x(df/2, 1/2) with x = df / (df + t^2) (regularised incomplete beta,
-// continued fraction in fp64).  One thread per k-mer.
+// continued fraction in fp64).  One thread per k-mer.  Validation, staging, the workspace, the copies back and the
+// top / second update are the shared ones of sp_kmertest.h.
 #define SP_TT_MAXG 64
 __device__ double d_betacf(double a, double b, double x) {
     const double tiny = 1e-300;
@@ -238,18 +240,16 @@ k7_ttest(const uint32_t *__restrict__ counts, long long M, int C, const double *
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= M) return;
     const uint32_t *row = counts + r * C;
-    int t1 = -1, t2 = -1;
-    double m1 = 0, m2 = 0;
+    sp_kt_best best;
     for (int g = 0; g < G; g++) {            // means in numpy's summation order; descending, ties in group order
         double v[SP_TT_MAXG];
         const int n = goff[g + 1] - goff[g];
         for (int i = 0; i < n; i++) v[i] = (double)row[gchrom[goff[g] + i]] / chrom_len[gchrom[goff[g] + i]];
         const double mean = d_np_sum(v, n) / (double)n;
         means[r * G + g] = mean;
-        if (t1 < 0 || mean > m1) { t2 = t1; m2 = m1; t1 = g; m1 = mean; }
-        else if (t2 < 0 || mean > m2) { t2 = g; m2 = mean; }
+        best = sp_kt_top2(g, mean, best);
     }
-    if (t2 < 0) t2 = t1;
+    const int t1 = best.t1, t2 = best.t2 < 0 ? best.t1 : best.t2;
     top[r] = t1;
     second[r] = t2;
     double var[2], mu[2];
@@ -268,7 +268,7 @@ k7_ttest(const uint32_t *__restrict__ counts, long long M, int C, const double *
     const double df = (double)(nn[0] + nn[1]) - 2.0;
     double p;
     if (!(df > 0.0)) {
-        p = __longlong_as_double(0x7ff8000000000000LL);
+        p = sp_kt_nan();
     } else {
         const double svar = ((nn[0] - 1) * var[0] + (nn[1] - 1) * var[1]) / df;
         const double denom = sqrt(svar * (1.0 / nn[0] + 1.0 / nn[1]));
@@ -283,59 +283,14 @@ k7_ttest(const uint32_t *__restrict__ counts, long long M, int C, const double *
 extern "C" int sp_kmer_ttest(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
                              const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                              double *pvals, double *means) {
-    if (!ctx || M < 0 || C < 1 || n_groups < 1 || !lengths || !group_off || !group_chrom ||
-        (M > 0 && (!counts || !top || !second || !pvals || !means)))
-        return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest: bad arguments");
-    for (int g = 0; g < n_groups; g++) {
-        const int n = group_off[g + 1] - group_off[g];
-        if (n < 1 || n > SP_TT_MAXG) return sp_fail(ctx, SP_EUNSUP, "sp_kmer_ttest: a subgenome with %d chromosomes (1..%d supported)", n, SP_TT_MAXG);
-        for (int j = group_off[g]; j < group_off[g + 1]; j++)
-            if (group_chrom[j] < 0 || group_chrom[j] >= C) return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest: chromosome index out of range");
-    }
-    if (M == 0) return SP_OK;
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nuc = (size_t)group_off[n_groups];
-    // `counts` may be a host or a DEVICE pointer (a caller that staged the rows earlier, Context.stage_rows): rows
-    // that already live on this device are read in place -- no second M x C copy inside the workspace
-    bool on_device = false;
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, counts) == hipSuccess)
-            on_device = at.type == hipMemoryTypeDevice && at.device == ctx->device;
-        else
-            (void)hipGetLastError();   // a plain malloc'ed pointer is "invalid value" for this query on some runtimes
-    }
-    const size_t rows_bytes = on_device ? 0 : al((size_t)M * C * 4);
-    const size_t need = rows_bytes + al((size_t)C * 8) + al((size_t)(n_groups + 1) * 4) + al(nuc * 4) +
-                        2 * al((size_t)M * 4) + al((size_t)M * 8) + al((size_t)M * n_groups * 8);
-    int rc = sp_buf_ensure(ctx, ctx->b_tt, (int64_t)need);
+    sp_kt_call k{ctx, "sp_kmer_ttest", counts, M, C, lengths, n_groups, group_off, group_chrom, top, second, pvals, means, nullptr};
+    int rc = sp_kt_check_groups(k, SP_TT_MAXG, SP_EUNSUP);
+    if (rc || M == 0) return rc;
+    rc = sp_kt_begin(k, false, [](sp_carve &) {});
     if (rc) return rc;
-    char *q = (char *)ctx->b_tt.p;
-    const uint32_t *d_counts = on_device ? counts : (const uint32_t *)q; q += rows_bytes;
-    double *d_len = (double *)q; q += al((size_t)C * 8);
-    int *d_goff = (int *)q; q += al((size_t)(n_groups + 1) * 4);
-    int *d_gch = (int *)q; q += al(nuc * 4);
-    int *d_top = (int *)q; q += al((size_t)M * 4);
-    int *d_sec = (int *)q; q += al((size_t)M * 4);
-    double *d_p = (double *)q; q += al((size_t)M * 8);
-    double *d_means = (double *)q;
-    std::vector<double> hl((size_t)C);
-    for (int c = 0; c < C; c++) hl[(size_t)c] = (double)lengths[c];
-    if (!on_device)
-        SP_HIP(ctx, hipMemcpyAsync((void *)d_counts, counts, (size_t)M * C * 4, hipMemcpyDefault, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_len, hl.data(), (size_t)C * 8, hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_goff, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_gch, group_chrom, nuc * 4, hipMemcpyHostToDevice, ctx->stream));
-    SP_LAUNCH(ctx, "k7_ttest", k7_ttest, dim3((unsigned)((M + 127) / 128)), dim3(128), 0, d_counts,
-              (long long)M, C, (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, d_top, d_sec, d_p,
-              d_means);
-    SP_HIP(ctx, hipMemcpyAsync(top, d_top, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(second, d_sec, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(pvals, d_p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(means, d_means, (size_t)M * n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SP_OK;
+    SP_LAUNCH(ctx, "k7_ttest", k7_ttest, dim3((unsigned)((M + 127) / 128)), dim3(128), 0, k.rows, (long long)M, C,
+              (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch, k.d.top, k.d.sec, k.d.p, k.d.means);
+    return sp_kt_finish(k);
 }
 
 // ----------------------------------------------------------------- f-1, subgenomes of more than SP_TT_MAXG chromosomes
@@ -432,21 +387,18 @@ k7_ttest_wide_means(const uint32_t *__restrict__ counts, long long M, int C, con
                     double *__restrict__ means) {
     __shared__ sp_tw_lds L;
     const long long r0 = (long long)blockIdx.x * SP_TW_ROWS, r = r0 + threadIdx.x;
-    int t1 = -1, t2 = -1;
-    double k1 = 0, k2 = 0;
+    sp_kt_best best;
     for (int g = 0; g < G; g++) {
         const int n = goff[g + 1] - goff[g];
         double seq;
         const double mean = tw_group<false>(L, counts, r0, M, C, chrom_len, gchrom + goff[g], n, prog + poff[g], 0.0, &seq) / (double)n;
         const double key = seq / (double)n;
         if (r < M) means[r * G + g] = mean;
-        if (t1 < 0 || key > k1) { t2 = t1; k2 = k1; t1 = g; k1 = key; }
-        else if (t2 < 0 || key > k2) { t2 = g; k2 = key; }
+        best = sp_kt_top2(g, key, best);
     }
-    if (t2 < 0) t2 = t1;
     if (r < M) {
-        top[r] = t1;
-        second[r] = t2;
+        top[r] = best.t1;
+        second[r] = best.t2 < 0 ? best.t1 : best.t2;
     }
 }
 
@@ -472,7 +424,7 @@ k7_ttest_wide_test(const uint32_t *__restrict__ counts, long long M, int C, cons
     const double df = (double)(n1 + n2) - 2.0;
     double p;
     if (!(df > 0.0)) {
-        p = __longlong_as_double(0x7ff8000000000000LL);
+        p = sp_kt_nan();
     } else {
         const double svar = ((n1 - 1) * var1 + (n2 - 1) * var2) / df;
         const double denom = sqrt(svar * (1.0 / n1 + 1.0 / n2));
@@ -487,77 +439,34 @@ k7_ttest_wide_test(const uint32_t *__restrict__ counts, long long M, int C, cons
 extern "C" int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
                                   const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                                   double *pvals, double *means) {
-    if (!ctx || M < 0 || C < 1 || n_groups < 1 || !lengths || !group_off || !group_chrom ||
-        (M > 0 && (!counts || !top || !second || !pvals || !means)))
-        return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest_wide: bad arguments");
-    std::vector<int> poff((size_t)n_groups + 1, 0);
-    for (int g = 0; g < n_groups; g++) {
-        const int n = group_off[g + 1] - group_off[g];
-        if (n < 1 || n > SP_TT_WIDE_MAX)
-            return sp_fail(ctx, SP_EUNSUP, "sp_kmer_ttest_wide: a subgenome with %d chromosomes (1..%d supported)", n, SP_TT_WIDE_MAX);
-        for (int j = group_off[g]; j < group_off[g + 1]; j++)
-            if (group_chrom[j] < 0 || group_chrom[j] >= C) return sp_fail(ctx, SP_EINVAL, "sp_kmer_ttest_wide: chromosome index out of range");
-        poff[(size_t)g + 1] = poff[(size_t)g] + n / 8;
-    }
-    if (M == 0) return SP_OK;
+    sp_kt_call k{ctx, "sp_kmer_ttest_wide", counts, M, C, lengths, n_groups, group_off, group_chrom, top, second, pvals, means, nullptr};
+    int rc = sp_kt_check_groups(k, SP_TT_WIDE_MAX, SP_EUNSUP);
+    if (rc || M == 0) return rc;
     // the summation program of every group: one byte per block of 8 values (sp_ttest.h)
+    std::vector<int> poff((size_t)n_groups + 1, 0);
+    for (int g = 0; g < n_groups; g++) poff[(size_t)g + 1] = poff[(size_t)g] + (group_off[g + 1] - group_off[g]) / 8;
     std::vector<uint8_t> hprog((size_t)poff[(size_t)n_groups] + 1, 0);
     for (int g = 0; g < n_groups; g++) {
         const int depth = sp_tt_program(group_off[g + 1] - group_off[g], hprog.data() + poff[(size_t)g]);
-        if (depth > SP_TT_DEPTH) return sp_fail(ctx, SP_EUNSUP, "sp_kmer_ttest_wide: summation stack of %d (%d supported)", depth, SP_TT_DEPTH);
+        if (depth > SP_TT_DEPTH) return sp_fail(ctx, SP_EUNSUP, "%s: summation stack of %d (%d supported)", k.who, depth, SP_TT_DEPTH);
     }
-    SP_HIP(ctx, hipSetDevice(ctx->device));
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t nuc = (size_t)group_off[n_groups];
-    bool on_device = false;      // rows staged on this device earlier are read in place, as in sp_kmer_ttest
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, counts) == hipSuccess)
-            on_device = at.type == hipMemoryTypeDevice && at.device == ctx->device;
-        else
-            (void)hipGetLastError();
-    }
-    const size_t rows_bytes = on_device ? 0 : al((size_t)M * C * 4);
-    const size_t need = rows_bytes + al((size_t)C * 8) + 2 * al((size_t)(n_groups + 1) * 4) + al(nuc * 4) + al(hprog.size()) +
-                        2 * al((size_t)M * 4) + al((size_t)M * 8) + al((size_t)M * n_groups * 8);
-    int rc = sp_buf_ensure(ctx, ctx->b_tt, (int64_t)need);
-    if (rc == SP_ENOMEM)
-        return sp_fail(ctx, SP_ENOMEM, "sp_kmer_ttest_wide: a workspace of %lld bytes (%lld rows x %d chromosomes%s) does not fit on the device",
-                       (long long)need, (long long)M, C, on_device ? ", rows already staged" : "");
+    int *d_poff;
+    uint8_t *d_prog;
+    rc = sp_kt_begin(k, false, [&](sp_carve &cv) {
+        d_poff = cv.take<int>((size_t)n_groups + 1);
+        d_prog = cv.take<uint8_t>(hprog.size());
+    });
     if (rc) return rc;
-    char *q = (char *)ctx->b_tt.p;
-    const uint32_t *d_counts = on_device ? counts : (const uint32_t *)q; q += rows_bytes;
-    double *d_len = (double *)q; q += al((size_t)C * 8);
-    int *d_goff = (int *)q; q += al((size_t)(n_groups + 1) * 4);
-    int *d_poff = (int *)q; q += al((size_t)(n_groups + 1) * 4);
-    int *d_gch = (int *)q; q += al(nuc * 4);
-    uint8_t *d_prog = (uint8_t *)q; q += al(hprog.size());
-    int *d_top = (int *)q; q += al((size_t)M * 4);
-    int *d_sec = (int *)q; q += al((size_t)M * 4);
-    double *d_p = (double *)q; q += al((size_t)M * 8);
-    double *d_means = (double *)q;
-    std::vector<double> hl((size_t)C);
-    for (int c = 0; c < C; c++) hl[(size_t)c] = (double)lengths[c];
-    if (!on_device)
-        SP_HIP(ctx, hipMemcpyAsync((void *)d_counts, counts, (size_t)M * C * 4, hipMemcpyDefault, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_len, hl.data(), (size_t)C * 8, hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_goff, group_off, (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_gch, group_chrom, nuc * 4, hipMemcpyHostToDevice, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(d_prog, hprog.data(), hprog.size(), hipMemcpyHostToDevice, ctx->stream));
     const dim3 grid((unsigned)((M + SP_TW_ROWS - 1) / SP_TW_ROWS));
-    SP_LAUNCH(ctx, "k7_ttest_wide_means", k7_ttest_wide_means, grid, dim3(SP_TW_ROWS), 0, d_counts, (long long)M, C,
-              (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, (const int *)d_poff,
-              (const uint8_t *)d_prog, d_top, d_sec, d_means);
-    SP_LAUNCH(ctx, "k7_ttest_wide_test", k7_ttest_wide_test, grid, dim3(SP_TW_ROWS), 0, d_counts, (long long)M, C,
-              (const double *)d_len, n_groups, (const int *)d_goff, (const int *)d_gch, (const int *)d_poff,
-              (const uint8_t *)d_prog, (const int *)d_top, (const int *)d_sec, (const double *)d_means, d_p);
-    SP_HIP(ctx, hipMemcpyAsync(top, d_top, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(second, d_sec, (size_t)M * 4, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(pvals, d_p, (size_t)M * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(means, d_means, (size_t)M * n_groups * 8, hipMemcpyDeviceToHost, ctx->stream));
-    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return SP_OK;
+    SP_LAUNCH(ctx, "k7_ttest_wide_means", k7_ttest_wide_means, grid, dim3(SP_TW_ROWS), 0, k.rows, (long long)M, C,
+              (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch, (const int *)d_poff,
+              (const uint8_t *)d_prog, k.d.top, k.d.sec, k.d.means);
+    SP_LAUNCH(ctx, "k7_ttest_wide_test", k7_ttest_wide_test, grid, dim3(SP_TW_ROWS), 0, k.rows, (long long)M, C,
+              (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch, (const int *)d_poff,
+              (const uint8_t *)d_prog, (const int *)k.d.top, (const int *)k.d.sec, (const double *)k.d.means, k.d.p);
+    return sp_kt_finish(k);
 }
 
 // column sums of the window table (Stats.py:142) + their sum, on the device

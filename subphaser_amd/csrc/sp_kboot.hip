@@ -126,14 +126,7 @@ extern "C" int sp_kmeans_bootstrap(sp_ctx *ctx, const double *z, int C, int64_t 
                            (long long)cols[i], (long long)(i / (size_t)n), (long long)M);
     if (R == 0) return SP_OK;
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    bool on_device = false;      // a matrix staged on this device earlier is read in place, as in sp_kmer_ttest
-    {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, z) == hipSuccess)
-            on_device = at.type == hipMemoryTypeDevice && at.device == ctx->device;
-        else
-            (void)hipGetLastError();
-    }
+    const bool on_device = sp_on_device(ctx, z);     // a matrix staged on this device earlier is read in place
     sp_carve sizes;
     auto layout = [&](sp_carve &cv, long long *&d_cols, int *&d_lab, int *&d_it, double *&d_gram) {
         d_cols = cv.take<long long>(ncols);

@@ -257,15 +257,9 @@ int kp_check(sp_ctx *ctx, const char *who, const uint32_t *counts, int64_t M, in
         if (lengths[c] <= 0) return sp_fail(ctx, SP_EINVAL, "%s: chromosome %d has length %lld", who, c, (long long)lengths[c]);
     return SP_OK;
 }
-bool kp_on_device(sp_ctx *ctx, const void *p) {
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) == hipSuccess) return at.type == hipMemoryTypeDevice && at.device == ctx->device;
-    (void)hipGetLastError();     // a plain malloc'ed pointer is "invalid value" for this query on some runtimes
-    return false;
-}
 // rows that already live on this device are read in place, as in sp_kmer_ttest; host rows are uploaded into `up`
 int kp_rows(sp_ctx *ctx, const char *who, const uint32_t *counts, int64_t M, int C, sp_tmp<uint32_t> &up, const uint32_t **out) {
-    if (kp_on_device(ctx, counts)) {
+    if (sp_on_device(ctx, counts)) {
         *out = counts;
         return SP_OK;
     }
