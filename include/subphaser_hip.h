@@ -271,6 +271,23 @@ int sp_kmer_ranktest(sp_ctx *ctx, const uint32_t *counts /*host or device*/, int
                      int n_groups, const int32_t *group_off, const int32_t *group_chrom,
                      int method /*0 kruskal, 1 mannwhitneyu*/, int32_t *top, int32_t *second, double *pvals,
                      double *means /*M x n_groups*/, double *stat /*M, or NULL*/);
+/* sp_kmer_ranktest for groups of 1 .. 4096 chromosomes (scaffold-level assemblies), same arguments, `counts` host or
+ * device.  means, top and second are those of sp_kmer_ttest_wide -- np.mean of the list, the order key -sum(x) / len(x)
+ * added left to right -- so a matrix gets the pair of groups the reference picks at any list length (sp_kmer_ranktest
+ * orders by the pairwise mean; the two agree except where two groups' keys meet in the last bits).  The test is the one
+ * of sp_kmer_ranktest; csrc/sp_rankwide.h states the arithmetic: the same doubled midranks, rank sums and tie term as
+ * 64-bit integers, found by sorting each group's values and bounding every value in both sorted lists, and the same
+ * statistics operation for operation -- at sizes both entries take, stat and p are the same bits.  The exact
+ * Mann-Whitney null serves every row without ties whose smaller group has at most 8 chromosomes, whatever the larger
+ * (tables built on the host in 128-bit integers per distinct size pair, every entry within 1 ulp of the exact fraction).
+ * k7_ranktest_wide is one workgroup per row: a bitonic sort of the two groups in LDS, binary searches, integer sums.
+ * SP_EINVAL: a NULL pointer, method outside 0..1, an empty group, a chromosome index outside [0, C), a length <= 0.
+ * SP_EUNSUP: a group of more than 4096 chromosomes (decided before any allocation; the message carries the size).
+ * SP_ENOMEM: the workspace does not fit (the message carries its size).  M == 0: SP_OK without a launch.          */
+int sp_kmer_ranktest_wide(sp_ctx *ctx, const uint32_t *counts /*host or device*/, int64_t M, int C, const int64_t *lengths,
+                          int n_groups, const int32_t *group_off, const int32_t *group_chrom,
+                          int method /*0 kruskal, 1 mannwhitneyu*/, int32_t *top, int32_t *second, double *pvals,
+                          double *means /*M x n_groups*/, double *stat /*M, or NULL*/);
 /* The same stage for test_method = wilcoxon, Cluster.py:178-194: arguments as in sp_kmer_ranktest without `method`
  * (`counts` a host or a device pointer: rows staged on this device are read in place); means, top and second are formed
  * exactly as sp_kmer_ttest and sp_kmer_ranktest form them.  The test is paired: every group has the same number n of

@@ -19,6 +19,7 @@ KBOOT_MAX_POINTS, KBOOT_MAX_CLUSTERS = 128, 32     # SP_KB_MAXC, SP_KB_MAXK in c
 KPCA_MAX_CHROM, KPCA_MAX_COMP = 1024, 32           # SP_KP_MAXC, SP_KP_MAXCOMP in csrc/sp_kpca.h
 HCLUST_MAX_POINTS = 16384                          # SP_HC_MAXP in csrc/sp_hclust.h
 RANKTEST_MAX_GROUP = 64                            # SP_RT_MAXG in csrc/sp_ranktest.h
+RANKTEST_WIDE_MAX_GROUP = 4096                     # SP_RW_MAXG in csrc/sp_rankwide.h
 RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: the `method` argument is the index
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
@@ -29,7 +30,7 @@ SYMBOLS = [
     "sp_count", "sp_count_range", "sp_count_recounts", "sp_nslots", "sp_tables_bind", "sp_table_overflow", "sp_table_merge", "sp_table_lengths", "sp_lengths", "sp_dump_size", "sp_dump",
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
-    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
+    "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_ranktest_wide", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -119,6 +120,7 @@ def load():
     L.sp_kmer_ttest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ttest_wide.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp]
     L.sp_kmer_ranktest.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.sp_kmer_ranktest_wide.argtypes = L.sp_kmer_ranktest.argtypes
     L.sp_kmer_wilcoxon.argtypes = [vp, vp, i64, ci, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.sp_kmeans_bootstrap.argtypes = [vp, vp, ci, i64, vp, ci, ci, ci, C.c_uint64, vp, vp, vp]
     L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
@@ -803,11 +805,24 @@ class Context:
         per group (ValueError beyond).  Returns (top, second, pvals, means [M, n_groups], stat): means, top and second as
         kmer_ttest gives them, stat the statistic (H, or U of the top group; NaN where the test has none), bit-defined
         by csrc/sp_ranktest.h."""
+        return self._kmer_test(self.L.sp_kmer_ranktest, counts, lengths, groups, extra=(self._ranktest_method(method),),
+                               want_stat=True)
+
+    @staticmethod
+    def _ranktest_method(method):
         if isinstance(method, str):
             if method not in RANKTEST_METHODS:
                 raise ValueError("method must be one of {}".format(RANKTEST_METHODS))
             method = RANKTEST_METHODS.index(method)
-        return self._kmer_test(self.L.sp_kmer_ranktest, counts, lengths, groups, extra=(int(method),), want_stat=True)
+        return int(method)
+
+    def kmer_ranktest_wide(self, counts, lengths, groups, method):
+        """kmer_ranktest for subgenomes of up to RANKTEST_WIDE_MAX_GROUP chromosomes (sp_kmer_ranktest_wide): same
+        arguments and results.  means, top and second are those of kmer_ttest_wide (np.mean of a group's list; the
+        reference's order key, the left-to-right sum over the list divided by its length); stat and p are bit-defined
+        by csrc/sp_rankwide.h and equal kmer_ranktest's where both take the sizes and pick the same pair."""
+        return self._kmer_test(self.L.sp_kmer_ranktest_wide, counts, lengths, groups, extra=(self._ranktest_method(method),),
+                               want_stat=True)
 
     def kmer_wilcoxon(self, counts, lengths, groups):
         """Cluster.output_kmers' per-k-mer test for test_method "wilcoxon" on the device (sp_kmer_wilcoxon).  counts,

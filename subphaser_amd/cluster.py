@@ -387,12 +387,14 @@ class Cluster:
         """(call, None) when a device engine of KMER_ENGINES applies -- call(rows, lengths, groups) returns (top, second,
         pvals, means[, stat]) -- else (None, why): the reason for the log, None where the method stays silent"""
         engines = KMER_ENGINES[test_method]
-        fits = [e for e in engines if e[2](groups) is None]
-        attr, extra, size_rule, says = fits[0] if fits else engines[-1]      # the first whose sizes fit
-        entry = getattr(ctx, attr, None)
-        if entry is None:
-            why = says if isinstance(says, str) else None
-            return None, why
+        have = [e for e in engines if getattr(ctx, e[0], None) is not None]
+        if not have:
+            says = engines[0][3]
+            return None, says if isinstance(says, str) else None
+        fits = [e for e in have if e[2](groups) is None]
+        # the first the context has whose sizes fit; else the widest it has, whose size rule is the reason
+        attr, extra, size_rule, says = fits[0] if fits else have[-1]
+        entry = getattr(ctx, attr)
         if getattr(self, "_counts", None) is None or self._lengths is None:
             why = "the matrix has no integer counts and lengths"
         elif not M:
@@ -484,12 +486,15 @@ def _wilcoxon_sizes(groups):
         return "subgenomes of {} chromosomes (the device engine takes 2 to {})".format(sizes[0], _native.WILCOXON_MAX_GROUP)
 
 
-# test_method -> its device engines, the first whose size rule passes is taken: (Context attribute, arguments behind the
-# group lists, size rule: groups -> None or why not, what the log says -- a string: every reason, this one for a context
-# without the entry; True: every reason but that one; False: nothing).
+# test_method -> its device engines, the first the context has whose size rule passes is taken: (Context attribute,
+# arguments behind the group lists, size rule: groups -> None or why not, what the log says -- a string: every reason,
+# this one for a context without the entry; True: every reason but that one; False: nothing).  When no size rule
+# passes, the last engine the context has gives the reason.
 #   ttest_ind     k7_ttest keeps a group's values in registers, up to TTEST_MAX_GROUP chromosomes (csrc/sp_enrich.hip);
 #                 scaffold-level runs with larger groups, up to TTEST_WIDE_MAX_GROUP, take k7_ttest_wide*
-#   rank-sum      k7_ranktest ranks the two chosen groups in LDS, up to RANKTEST_MAX_GROUP each (csrc/sp_ranktest.hip)
+#   rank-sum      k7_ranktest ranks the two chosen groups in LDS, up to RANKTEST_MAX_GROUP each (csrc/sp_ranktest.hip);
+#                 larger groups, up to RANKTEST_WIDE_MAX_GROUP, take k7_ranktest_wide, a workgroup per k-mer
+#                 (csrc/sp_rankwide.hip)
 #   wilcoxon      k7_wilcoxon: every subgenome has the same number of chromosomes, 2 .. WILCOXON_MAX_GROUP
 #                 (csrc/sp_wilcoxon.hip); unequal sizes reach scipy, which raises
 KMER_ENGINES = {
@@ -499,6 +504,8 @@ KMER_ENGINES = {
 }
 for _m in _native.RANKTEST_METHODS:
     KMER_ENGINES[_m] = [("kmer_ranktest", (_m,), _groups_upto(lambda: _native.RANKTEST_MAX_GROUP),
+                         "no device context with the rank-sum tests"),
+                        ("kmer_ranktest_wide", (_m,), _groups_upto(lambda: _native.RANKTEST_WIDE_MAX_GROUP),
                          "no device context with the rank-sum tests")]
 
 

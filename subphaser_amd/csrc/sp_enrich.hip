@@ -8,6 +8,7 @@
 // margins of 2e8 where a difference of lgamma() values loses 6-7 digits; the
 // tail is then summed by the exact term recurrence.  All arithmetic is fp64.
 #include "sp_device.h"
+#include "sp_internal.h"
 #include "sp_kmertest.h"
 #include "sp_ttest.h"
 
@@ -436,36 +437,50 @@ k7_ttest_wide_test(const uint32_t *__restrict__ counts, long long M, int C, cons
     if (r < M) pvals[r] = p;
 }
 
+// pass 1 for the other units (sp_internal.h): the summation program of every group, one byte per block of 8 values
+// (sp_ttest.h), and the launch of k7_ttest_wide_means on it
+int sp_tw_means_plan(sp_ctx *ctx, const char *who, int n_groups, const int32_t *group_off, sp_tw_plan &plan) {
+    plan.poff.assign((size_t)n_groups + 1, 0);
+    for (int g = 0; g < n_groups; g++) plan.poff[(size_t)g + 1] = plan.poff[(size_t)g] + (group_off[g + 1] - group_off[g]) / 8;
+    plan.prog.assign((size_t)plan.poff[(size_t)n_groups] + 1, 0);
+    for (int g = 0; g < n_groups; g++) {
+        const int depth = sp_tt_program(group_off[g + 1] - group_off[g], plan.prog.data() + plan.poff[(size_t)g]);
+        if (depth > SP_TT_DEPTH) return sp_fail(ctx, SP_EUNSUP, "%s: summation stack of %d (%d supported)", who, depth, SP_TT_DEPTH);
+    }
+    return SP_OK;
+}
+int sp_tw_means_launch(sp_ctx *ctx, const sp_tw_plan &plan, int *d_poff, uint8_t *d_prog, const uint32_t *rows, int64_t M, int C,
+                       const double *d_len, int n_groups, const int *d_goff, const int *d_gch, int *d_top, int *d_sec,
+                       double *d_means) {
+    SP_HIP(ctx, hipMemcpyAsync(d_poff, plan.poff.data(), plan.poff.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    SP_HIP(ctx, hipMemcpyAsync(d_prog, plan.prog.data(), plan.prog.size(), hipMemcpyHostToDevice, ctx->stream));
+    SP_LAUNCH(ctx, "k7_ttest_wide_means", k7_ttest_wide_means, dim3((unsigned)((M + SP_TW_ROWS - 1) / SP_TW_ROWS)), dim3(SP_TW_ROWS),
+              0, rows, (long long)M, C, d_len, n_groups, d_goff, d_gch, (const int *)d_poff, (const uint8_t *)d_prog, d_top,
+              d_sec, d_means);
+    return SP_OK;
+}
+
 extern "C" int sp_kmer_ttest_wide(sp_ctx *ctx, const uint32_t *counts, int64_t M, int C, const int64_t *lengths, int n_groups,
                                   const int32_t *group_off, const int32_t *group_chrom, int32_t *top, int32_t *second,
                                   double *pvals, double *means) {
     sp_kt_call k{ctx, "sp_kmer_ttest_wide", counts, M, C, lengths, n_groups, group_off, group_chrom, top, second, pvals, means, nullptr};
     int rc = sp_kt_check_groups(k, SP_TT_WIDE_MAX, SP_EUNSUP);
     if (rc || M == 0) return rc;
-    // the summation program of every group: one byte per block of 8 values (sp_ttest.h)
-    std::vector<int> poff((size_t)n_groups + 1, 0);
-    for (int g = 0; g < n_groups; g++) poff[(size_t)g + 1] = poff[(size_t)g] + (group_off[g + 1] - group_off[g]) / 8;
-    std::vector<uint8_t> hprog((size_t)poff[(size_t)n_groups] + 1, 0);
-    for (int g = 0; g < n_groups; g++) {
-        const int depth = sp_tt_program(group_off[g + 1] - group_off[g], hprog.data() + poff[(size_t)g]);
-        if (depth > SP_TT_DEPTH) return sp_fail(ctx, SP_EUNSUP, "%s: summation stack of %d (%d supported)", k.who, depth, SP_TT_DEPTH);
-    }
+    sp_tw_plan plan;
+    rc = sp_tw_means_plan(ctx, k.who, n_groups, group_off, plan);
+    if (rc) return rc;
     int *d_poff;
     uint8_t *d_prog;
     rc = sp_kt_begin(k, false, [&](sp_carve &cv) {
-        d_poff = cv.take<int>((size_t)n_groups + 1);
-        d_prog = cv.take<uint8_t>(hprog.size());
+        d_poff = cv.take<int>(plan.poff.size());
+        d_prog = cv.take<uint8_t>(plan.prog.size());
     });
     if (rc) return rc;
-    SP_HIP(ctx, hipMemcpyAsync(d_poff, poff.data(), (size_t)(n_groups + 1) * 4, hipMemcpyHostToDevice, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_prog, hprog.data(), hprog.size(), hipMemcpyHostToDevice, ctx->stream));
-    const dim3 grid((unsigned)((M + SP_TW_ROWS - 1) / SP_TW_ROWS));
-    SP_LAUNCH(ctx, "k7_ttest_wide_means", k7_ttest_wide_means, grid, dim3(SP_TW_ROWS), 0, k.rows, (long long)M, C,
-              (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch, (const int *)d_poff,
-              (const uint8_t *)d_prog, k.d.top, k.d.sec, k.d.means);
-    SP_LAUNCH(ctx, "k7_ttest_wide_test", k7_ttest_wide_test, grid, dim3(SP_TW_ROWS), 0, k.rows, (long long)M, C,
-              (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch, (const int *)d_poff,
-              (const uint8_t *)d_prog, (const int *)k.d.top, (const int *)k.d.sec, (const double *)k.d.means, k.d.p);
+    rc = sp_tw_means_launch(ctx, plan, d_poff, d_prog, k.rows, M, C, k.d.len, n_groups, k.d.goff, k.d.gch, k.d.top, k.d.sec, k.d.means);
+    if (rc) return rc;
+    SP_LAUNCH(ctx, "k7_ttest_wide_test", k7_ttest_wide_test, dim3((unsigned)((M + SP_TW_ROWS - 1) / SP_TW_ROWS)), dim3(SP_TW_ROWS), 0,
+              k.rows, (long long)M, C, (const double *)k.d.len, n_groups, (const int *)k.d.goff, (const int *)k.d.gch,
+              (const int *)d_poff, (const uint8_t *)d_prog, (const int *)k.d.top, (const int *)k.d.sec, (const double *)k.d.means, k.d.p);
     return sp_kt_finish(k);
 }
 

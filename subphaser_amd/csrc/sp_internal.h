@@ -48,5 +48,20 @@ int sp_sparse_filter(sp_ctx *ctx, int n_sets, const int32_t *set_off, const int3
                      double ratio);
 int sp_sparse_fetch(sp_ctx *ctx, bool hist, uint64_t *keys, uint32_t *counts, double *freqs, uint64_t *tot, bool async);
 
+// sp_enrich.hip: pass 1 of the k-mer tests for wide groups (k7_ttest_wide_means): means[r][g] = np.mean of the group's
+// list, top / second by the reference's order key.  sp_tw_means_plan builds the groups' summation programs on the host
+// (SP_EUNSUP with `who` in the message when a group needs a deeper stack than the kernel has); the caller carves
+// plan.poff.size() ints and plan.prog.size() bytes behind its own arrays, and sp_tw_means_launch uploads the programs
+// and launches the kernel on the context's stream.  The plan is the source of asynchronous copies: it lives until the
+// caller has waited for the stream.
+struct sp_tw_plan {
+    std::vector<int> poff;          // [n_groups + 1]: where a group's program starts
+    std::vector<uint8_t> prog;
+};
+int sp_tw_means_plan(sp_ctx *ctx, const char *who, int n_groups, const int32_t *group_off, sp_tw_plan &plan);
+int sp_tw_means_launch(sp_ctx *ctx, const sp_tw_plan &plan, int *d_poff, uint8_t *d_prog, const uint32_t *rows, int64_t M, int C,
+                       const double *d_len, int n_groups, const int *d_goff, const int *d_gch, int *d_top, int *d_sec,
+                       double *d_means);
+
 // sp_map.hip
 int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n);

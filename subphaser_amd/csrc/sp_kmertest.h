@@ -1,5 +1,6 @@
 // sp_kmertest.h -- what the per-k-mer tests of Cluster.output_kmers share: sp_kmer_ttest and sp_kmer_ttest_wide
-// (sp_enrich.hip), sp_kmer_ranktest (sp_ranktest.hip) and sp_kmer_wilcoxon (sp_wilcoxon.hip).  Included from .hip units only.
+// (sp_enrich.hip), sp_kmer_ranktest (sp_ranktest.hip), sp_kmer_ranktest_wide (sp_rankwide.hip) and sp_kmer_wilcoxon
+// (sp_wilcoxon.hip).  Included from .hip units only.
 //   host    sp_kt_check_groups / sp_kt_check_lengths validate the arguments; sp_kt_begin decides whether the rows are read
 //           in place (sp_on_device), lays the workspace out in ctx->b_tt (sp_ktlayout.h: the common arrays, then the
 //           entry's own through its hook) and uploads lengths, lists and host rows; sp_kt_finish copies the results back
@@ -65,10 +66,12 @@ int sp_kt_begin(sp_kt_call &k, bool with_stat, Extra &&extra) {
     sp_carve sizes;
     const size_t need = sp_kt_layout(sizes, shape, k.d, extra);
     const int rc = sp_buf_ensure(ctx, ctx->b_tt, (int64_t)need);
-    if (rc == SP_ENOMEM)
+    if (rc == SP_ENOMEM) {
+        (void)hipGetLastError();     // or the context's next launch check would report this allocation
         return sp_fail(ctx, SP_ENOMEM, "%s: a workspace of %lld bytes (%lld rows x %d chromosomes%s, %d groups) does not fit on the device",
                        k.who, (long long)need, (long long)k.M, k.C, shape.rows_on_device ? ", read in place" : " and their upload",
                        k.n_groups);
+    }
     if (rc) return rc;
     sp_carve cv(ctx->b_tt.p);
     sp_kt_layout(cv, shape, k.d, extra);

@@ -1,16 +1,19 @@
 #!/usr/bin/env python
 """The per-k-mer tests of Cluster.output_kmers (-test_method) on the device against the host path on the same machine.
 
-    python tools/kmertest_bench.py --method ttest_ind|ttest_wide|kruskal|mannwhitneyu|wilcoxon [--shape CxMxG]
+    python tools/kmertest_bench.py --method ttest_ind|ttest_wide|kruskal|mannwhitneyu|kruskal_wide|mannwhitneyu_wide|wilcoxon
+                                   [--shape CxMxG]
                                    [--reps 7] [--host-reps 1] [--no-host] [--host-rows N] [--worst 26x2200000x2] [--json]
 
 A shape is C chromosomes x M k-mers x G groups of C / G chromosomes (the last group takes the remainder; wilcoxon needs
 equal groups).  The default is the wheat shape 21x2200000x3 with planted subgenome structure (tests/kpca_ref.py
 `planted`: Poisson counts, every k-mer enriched in one group); ttest_wide defaults to the scaffold shape 3000x200000x3
-(Poisson counts around 30, every group the top one on some rows).  Printed: staging the rows (M x C x 4 bytes, what the
+(Poisson counts around 30, every group the top one on some rows), kruskal_wide and mannwhitneyu_wide to 600x200000x3, three
+subgenomes of 200 scaffolds, with the same counts.  Printed: staging the rows (M x C x 4 bytes, what the
 CLI pays before the k-mer test anyway), the call on staged rows and from host rows (median, minimum and maximum of the
 repeats), every kernel alone from sp_prof_report (a run of its own with the profiler on), cluster.numpy_kmer_test on the
-fp64 matrix (on the first --host-rows rows if given) and how far the two agree: top / second, NaN positions, the largest
+fp64 matrix (on the first --host-rows rows if given; skipped with a line when four fp64 copies of those rows exceed the
+memory available) and how far the two agree: top / second, NaN positions, the largest
 relative p difference, rows whose means differ in the last bits.  --worst (wilcoxon only) adds the worst case of the
 permutation branch: counts in 0..2 over equal lengths at 13 pairs, where nearly every row walks all 2^m sign
 assignments; its host path runs on the first 200000 rows.  --json ends with one line of the per-call times."""
@@ -36,6 +39,21 @@ METHODS = {
     "mannwhitneyu": (lambda ctx, *a: ctx.kmer_ranktest(*a, "mannwhitneyu"), ["k7_ranktest"], "mannwhitneyu"),
     "wilcoxon": (lambda ctx, *a: ctx.kmer_wilcoxon(*a), ["k7_wilcoxon"], "wilcoxon"),
 }
+for _m in ("kruskal", "mannwhitneyu"):
+    METHODS[_m + "_wide"] = (lambda ctx, *a, _m=_m: ctx.kmer_ranktest_wide(*a, _m), ["k7_ttest_wide_means", "k7_ranktest_wide"], _m)
+WIDE = ("ttest_wide", "kruskal_wide", "mannwhitneyu_wide")
+
+
+def mem_available():
+    """bytes of host memory available, or None where /proc/meminfo does not say"""
+    try:
+        with open("/proc/meminfo") as f:
+            for line in f:
+                if line.startswith("MemAvailable:"):
+                    return int(line.split()[1]) * 1024
+    except OSError:
+        pass
+    return None
 
 
 def timed(f, n):
@@ -59,7 +77,7 @@ def case(method, shape, worst=False):
     groups = [list(range(g * n, g * n + sizes[g])) for g in range(G)]
     if worst:
         return np.random.default_rng(13).integers(0, 3, (M, C)).astype(np.uint32), np.full(C, 1 << 21, np.int64), groups
-    if method == "ttest_wide":
+    if method in WIDE:
         rng = np.random.default_rng(2000)
         lengths = rng.integers(10**6, 10**8, C)
         counts = rng.poisson(30, (M, C)).astype(np.uint32)
@@ -100,6 +118,11 @@ def run(ctx, name, method, counts, lengths, groups, a, host_rows=None):
     if a.no_host:
         return times
     R = M if host_rows is None else min(M, host_rows)
+    avail = mem_available()
+    if avail is not None and 4 * R * C * 8 > avail:      # the fp64 matrix, the two groups' copies, their ranks
+        print("%s: numpy_kmer_test skipped: four fp64 copies of %d x %d values are %.1f GB, %.1f GB are available"
+              % (name, R, C, 4 * R * C * 8 / 1e9, avail / 1e9), flush=True)
+        return times
     freqs = counts[:R] / lengths.astype(np.float64)
     t_np, (ht, hs, hp, hm) = timed(lambda: cluster.numpy_kmer_test(freqs, groups, host_method), a.host_reps)
     with np.errstate(all="ignore"):
@@ -124,7 +147,8 @@ def main():
     ap.add_argument("--worst", default="26x2200000x2", help="wilcoxon: CxMxG of the permutation branch's worst case ('' skips it)")
     ap.add_argument("--json", action="store_true")
     a = ap.parse_args()
-    shape = a.shape or ("3000x200000x3" if a.method == "ttest_wide" else "21x2200000x3")
+    shape = a.shape or {"ttest_wide": "3000x200000x3", "kruskal_wide": "600x200000x3", "mannwhitneyu_wide": "600x200000x3"}.get(
+        a.method, "21x2200000x3")
     ctx = _native.Context(0)
     try:
         times = [run(ctx, "default shape" if not a.shape else a.shape, a.method, *case(a.method, shape), a, a.host_rows)]
