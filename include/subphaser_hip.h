@@ -385,6 +385,31 @@ int sp_sparse_export(sp_ctx *ctx, int chrom, int64_t first, int64_t count, void 
 int sp_sparse_view(sp_ctx *ctx, int C, const void *const *d_keys, const void *const *d_counts, const int64_t *n,
                    const int64_t *lengths, int k, int lower_count);
 
+/* ---- homoeologous blocks from shared single-copy k-mers --------------------
+ * Replaces the aligner runs of step_blocks (__main__.py:699-713, Blocks.py:7-56: minimap2 / unimap on every pair of
+ * homoeologous chromosomes) and the alignment filter of Circos.paf2blocks (Circos.py:654-682) by an anchor vote over
+ * the packed genome; the definition -- k-mer, sampling, single copy, anchor, vote, all integers -- is in
+ * csrc/sp_blocks.h.  block_k odd in 17..31, block_sample 0..16, bin >= 1, chromosomes below 2^31 - 16 bases.
+ *   sp_blocks_index    builds the index of one chromosome (kept until sp_blocks_release, a new sequence for the
+ *                      chromosome, sp_genome_reset or the end of the context; a second call with the same block_k and
+ *                      block_sample returns the stored tallies): n_sampled = valid sampled starts, n_single =
+ *                      single-copy keys
+ *   sp_blocks_pair     the vote of the ordered pair (a, b), both indexed with these block_k / block_sample: win_b
+ *                      (-1: no anchor), opp, votes, total of ceil(len(a) / bin) entries each, caller-owned;
+ *                      n_anchors = sum of total; n_spilled (may be NULL) = windows with more distinct cells than
+ *                      the LDS table holds, tallied again by band passes
+ *   sp_blocks_anchors  the n = n_anchors anchors of the last pair in ascending pos_a (tests and small inputs: it scans
+ *                      chromosome a twice more)
+ *   sp_blocks_release  frees the index of `chrom`, or every index with chrom < 0
+ *   sp_blocks_set_cells  cells of the per-window LDS table, a power of two in 2..4096 (default 4096); tests use small
+ *                      values to reach the band passes on small inputs -- the results do not depend on it         */
+int sp_blocks_index(sp_ctx *ctx, int chrom, int block_k, int block_sample, int64_t *n_sampled, int64_t *n_single);
+int sp_blocks_pair(sp_ctx *ctx, int a, int b, int block_k, int block_sample, int64_t bin, int32_t *win_b, uint8_t *opp,
+                   int32_t *votes, int32_t *total, int64_t *n_anchors, int64_t *n_spilled);
+int sp_blocks_anchors(sp_ctx *ctx, int32_t *pos_a, int32_t *pos_b, uint8_t *opp, int64_t n);
+int sp_blocks_release(sp_ctx *ctx, int chrom);
+int sp_blocks_set_cells(sp_ctx *ctx, int cells);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

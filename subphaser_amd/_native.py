@@ -21,6 +21,7 @@ HCLUST_MAX_POINTS = 16384                          # SP_HC_MAXP in csrc/sp_hclus
 RANKTEST_MAX_GROUP = 64                            # SP_RT_MAXG in csrc/sp_ranktest.h
 RANKTEST_WIDE_MAX_GROUP = 4096                     # SP_RW_MAXG in csrc/sp_rankwide.h
 RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: the `method` argument is the index
+BLOCKS_K_RANGE, BLOCKS_MAX_SAMPLE = (17, 31), 16   # SP_BK_KMIN, SP_BK_KMAX (odd only), SP_BK_SMAX in csrc/sp_blocks.h
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
@@ -31,6 +32,7 @@ SYMBOLS = [
     "sp_filter_view", "sp_filter", "sp_filter_fetch", "sp_filter_fetch_async", "sp_filter_fetch_wait", "sp_filter_fetch_device", "sp_filter_hist",
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
     "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_ranktest_wide", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
+    "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -126,6 +128,11 @@ def load():
     L.sp_kmer_pca_gram.argtypes = [vp, vp, i64, ci, vp, vp, P(i64), vp]
     L.sp_kmer_pca_signs.argtypes = [vp, vp, i64, ci, vp, vp, ci, vp, vp]
     L.sp_hclust_complete.argtypes = [vp, vp, ci, ci, vp, vp]
+    L.sp_blocks_index.argtypes = [vp, ci, ci, ci, P(i64), P(i64)]
+    L.sp_blocks_pair.argtypes = [vp, ci, ci, ci, ci, i64, vp, vp, vp, vp, P(i64), P(i64)]
+    L.sp_blocks_anchors.argtypes = [vp, vp, vp, vp, i64]
+    L.sp_blocks_release.argtypes = [vp, ci]
+    L.sp_blocks_set_cells.argtypes = [vp, ci]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -912,6 +919,43 @@ class Context:
         dist = np.empty((P, P), np.float64) if want_dist and P <= HCLUST_MAX_POINTS else None
         self._ck(self.L.sp_hclust_complete(self.h, _p(points), int(P), int(D), _p(merges), _p(dist)))
         return (merges, dist) if want_dist else merges
+
+    # -------------------------------------------------------------- homoeologous blocks
+    def blocks_index(self, chrom, block_k, block_sample):
+        """Index of the sampled single-copy k-mers of one chromosome (sp_blocks_index; definition in csrc/sp_blocks.h):
+        (n_sampled, n_single).  It stays on the device until blocks_release, a new sequence or genome_reset."""
+        ns, n1 = C.c_int64(), C.c_int64()
+        self._ck(self.L.sp_blocks_index(self.h, int(chrom), int(block_k), int(block_sample), C.byref(ns), C.byref(n1)))
+        return ns.value, n1.value
+
+    def blocks_pair(self, a, b, block_k, block_sample, bin_size, want_spilled=False):
+        """Anchor vote of the ordered pair (a, b), both indexed (sp_blocks_pair): win_b int32 (-1: no anchor), opp uint8,
+        votes int32, total int32 -- one entry per window of `bin_size` bases of a -- and the number of anchors."""
+        if int(bin_size) < 1:
+            raise ValueError("sp_blocks_pair: block_bin = %d is below 1" % int(bin_size))
+        n_win = -(-self.genome_len(a) // int(bin_size)) if 0 <= int(a) < self.n_chrom else 0
+        win_b, opp = np.empty(n_win, np.int32), np.empty(n_win, np.uint8)
+        votes, total = np.empty(n_win, np.int32), np.empty(n_win, np.int32)
+        n, sp = C.c_int64(), C.c_int64()
+        self._ck(self.L.sp_blocks_pair(self.h, int(a), int(b), int(block_k), int(block_sample), int(bin_size), _p(win_b), _p(opp),
+                                       _p(votes), _p(total), C.byref(n), C.byref(sp)))
+        return (win_b, opp, votes, total, n.value) + ((sp.value,) if want_spilled else ())
+
+    def blocks_anchors(self, n):
+        """The n anchors of the last blocks_pair, ascending pos_a: (pos_a int32, pos_b int32, opp uint8).  For tests and
+        small inputs: it scans chromosome a twice more."""
+        pa, pb, opp = np.empty(int(n), np.int32), np.empty(int(n), np.int32), np.empty(int(n), np.uint8)
+        self._ck(self.L.sp_blocks_anchors(self.h, _p(pa), _p(pb), _p(opp), int(n)))
+        return pa, pb, opp
+
+    def blocks_release(self, chrom=-1):
+        """free the block index of one chromosome, or of all"""
+        self._ck(self.L.sp_blocks_release(self.h, int(chrom)))
+
+    def blocks_set_cells(self, cells):
+        """cells of the pair kernel's per-window table (a power of two, 2..4096): a small value sends small inputs through
+        the band passes; results do not depend on it"""
+        self._ck(self.L.sp_blocks_set_cells(self.h, int(cells)))
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

@@ -83,6 +83,8 @@ struct sp_tabref {
     const uint32_t *ovf_idx = nullptr;
 };
 
+struct sp_blocks_state;   // sp_blocks.hip
+
 struct sp_prof_entry {
     std::string name;
     hipEvent_t e0, e1;
@@ -205,6 +207,7 @@ struct sp_ctx {
     sp_buf b_kp;            // k-mer PCA: lengths, row statistics, chunk partials, sign candidates (sp_kpca.hip)
     sp_buf b_hc;            // heatmap clustering: points, the P x P distance matrix, merges, chain state (sp_hclust.hip)
     sp_buf b_wtab, b_enr;   // window table (device) and the enrichment outputs
+    sp_blocks_state *blocks = nullptr;   // per-chromosome single-copy k-mer indexes of the block stage (sp_blocks.hip)
     sp_buf b_fq;      // global slow queue of the filter
     sp_buf b_fflat;   // flat set tables of the filter (sp_filter.hip)
     sp_buf b_map, b_mapdesc, b_ival, b_emit, b_fpar, b_win;  // reusable device buffers of sp_map_bins / k3_emit / sp_filter / stack

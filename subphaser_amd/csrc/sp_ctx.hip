@@ -146,6 +146,7 @@ int sp_ctx_destroy(sp_ctx *ctx) {
     for (auto &c : ctx->chroms) free_chrom(c);
     free_filter(ctx);
     sp_sparse_release(ctx);
+    sp_blocks_destroy(ctx);
     if (ctx->d_label) hipFree(ctx->d_label);
     if (ctx->d_bloom) hipFree(ctx->d_bloom);
     if (ctx->d_scratch) hipFree(ctx->d_scratch);
@@ -214,6 +215,7 @@ int sp_genome_reset(sp_ctx *ctx, int n_chrom) {
     if (!ctx || n_chrom < 0) return sp_fail(ctx, SP_EINVAL, "sp_genome_reset: bad arguments");
     SP_HIP(ctx, hipSetDevice(ctx->device));
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+    sp_blocks_drop(ctx, -1);
     if ((size_t)n_chrom == ctx->chroms.size()) {
         // same shape as before: keep every device buffer (packed genome, tables) for reuse
         for (auto &c : ctx->chroms) {
@@ -322,6 +324,7 @@ k0_unpack(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, int6
 
 static int genome_add_impl(sp_ctx *ctx, int chrom, const uint8_t *d_ascii, int64_t len) {
     sp_chrom &c = ctx->chroms[(size_t)chrom];
+    sp_blocks_drop(ctx, chrom);
     c.len = len;
     c.length_sum = 0;
     c.n_dump = 0;

@@ -63,5 +63,9 @@ int sp_tw_means_launch(sp_ctx *ctx, const sp_tw_plan &plan, int *d_poff, uint8_t
                        const double *d_len, int n_groups, const int *d_goff, const int *d_gch, int *d_top, int *d_sec,
                        double *d_means);
 
+// sp_blocks.hip: the indexes of a chromosome (chrom < 0: of all) go when its sequence does; everything at sp_ctx_destroy
+void sp_blocks_drop(sp_ctx *ctx, int chrom);
+void sp_blocks_destroy(sp_ctx *ctx);
+
 // sp_map.hip
 int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n);

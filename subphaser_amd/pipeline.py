@@ -1,5 +1,5 @@
 """`subphaser` command line for modules 1-2: ingest -> count -> matrix/filter -> cluster -> bin map ->
-window enrichment -> custom features, on the MI355X hot path.
+window enrichment -> custom features -> homoeologous blocks, on the MI355X hot path.
 
 What is kept from the reference is its CONTRACT: the flag surface (subphaser/__main__.py:29-248), the names
 and formats of the files under `-o` / `-tmpdir` and the checkpoint files, so that
@@ -8,6 +8,13 @@ How the run is organised is this build's own: a `Layout` that owns every path, f
 inputs and outputs, and a second half that never leaves the device between the bin map, the window stack
 and the Fisher tests -- `.subgenome.bin.count` is written FROM the device arrays as an output, it is not
 parsed back (the reference re-reads it with Circos.stack_matrix before it can enrich).
+
+Of modules 3-4 one step is here: the homoeologous blocks of the circos figure's innermost ring (step_blocks,
+__main__.py:699-713).  The reference runs an aligner on every pair of homoeologous chromosomes; stage_blocks votes
+over the single-copy k-mers two chromosomes share, on the packed genome the map stage has just walked (blocks.py,
+csrc/sp_blocks.hip), and writes `blocks.tsv`, `block_link.txt` (the format of Circos.paf2blocks) and a figure.  It
+runs unless -just_core, -disable_circos or -disable_blocks is given; the LTR module and the circos figure itself
+stay with the reference.
 """
 import argparse
 import io
@@ -21,6 +28,7 @@ from collections import Counter, OrderedDict
 import numpy as np
 
 from . import REFERENCE_VERSION, __version__
+from . import blocks as blocks_mod
 from . import circos, seqs, stats
 from .cluster import BOOTSTRAP_ENGINES, TEST_METHODS, Cluster
 from .config import SGConfig, check_duplicates, parse_idmap
@@ -84,7 +92,8 @@ CLI = [
                                   help="k-mers sampled for the clustered heatmap (the reference's constant); 0: no heatmap")),
         (("-just_core",), _FLAG),
     ]),
-    ("LTR / Circos", "accepted for command-line compatibility; modules 3-4 stay with the reference",
+    ("LTR / Circos", "accepted for command-line compatibility; modules 3-4 stay with the reference, except the homoeologous "
+                     "blocks (-disable_blocks, -min_block, -alt_cfgs are used; see Blocks)",
      [((o,), _STR) for o in ("-ltr_finder_options", "-ltr_harvest_options", "-tesorter_options", "-trimal_options",
                              "-tree_method", "-tree_options", "-ggtree_options", "-aligner", "-aligner_options",
                              "-chr_ordered")]
@@ -93,7 +102,19 @@ CLI = [
                                 "-disable_ltrtree", "-disable_circos", "-disable_blocks")]
      + [(("-mu",), dict(type=float, default=13e-9)), (("-subsample",), dict(type=int, default=1000)),
         (("-window_size",), dict(type=int, metavar="INT", default=1000000)),
-        (("-min_block",), dict(type=int, default=100000))]),
+        (("-min_block",), dict(type=int, default=blocks_mod.MIN_BLOCK,
+                               help="shortest homoeologous block (span on the first chromosome of the pair) that is kept"))]),
+    ("Blocks", "homoeologous blocks from shared single-copy k-mers (replaces the aligner of the reference's step_blocks; "
+               "-aligner / -aligner_options are accepted and run nothing).  The defaults are provisional", [
+        (("-block_k",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_K, help="anchor k-mer size, odd, 17..31")),
+        (("-block_sample",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_SAMPLE,
+                                  help="one k-mer in 2^INT is an anchor candidate (0..16)")),
+        (("-block_bin",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_BIN, help="voting window in bases")),
+        (("-block_votes",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_VOTES,
+                                 help="anchors the winning cell of a window needs for the window to be called")),
+        (("-block_gap",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_GAP,
+                               help="windows a block may skip, and drift off its diagonal, between two called windows")),
+    ]),
     ("Other options", None, [
         (("-p", "-ncpu"), dict(dest="ncpu", type=int, metavar="INT", default=NCPU)),
         (("-max_memory",), dict(type=str, metavar="MEM", default=None)),
@@ -541,6 +562,77 @@ class Pipeline:
         for sg, n in sorted(Counter(enriched.values()).items()):
             logger.info("\t{} {}-specific features".format(n, sg))
 
+    # ---- stage 6: homoeologous blocks ------------------------------------------------------------------------
+    def stage_blocks(self, lay, labels, d_size, cl=None):
+        """`blocks.tsv`, `block_link.txt` and `blocks.<figfmt>` from the anchor vote of every homoeologous pair (the pair
+        list of Blocks.run_align over the config lines, or over -alt_cfgs).  A failure costs these files and nothing else."""
+        for opt in ("aligner", "aligner_options"):
+            if getattr(self, opt, None):
+                logger.warning("-{} {}: no aligner is run; blocks come from shared single-copy k-mers".format(opt, getattr(self, opt)))
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            logger.info("blocks skipped: the stage runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
+            return
+        ctx = get_context()
+        if not all(hasattr(ctx, m) for m in ("blocks_index", "blocks_pair", "blocks_release")):
+            logger.info("blocks skipped: this context has no block entries")
+            return
+        try:
+            sgs = self.sgs
+            if getattr(self, "alt_cfgs", None):      # another grouping for this stage only (__main__.py:280-286)
+                rename = (getattr(self, "d_targets", None) or {}).get
+                sgs = [[[rename(c, c) for c in unit] for unit in line]
+                       for f in self.alt_cfgs for line in SGConfig(f, sep=self.sep).sgs]
+            known = set(labels)
+            lines = []
+            for line in sgs:
+                if len(line) < 2:
+                    logger.info("blocks: config line {} has a single unit, no pair to compare".format(line))
+                    lines.append([])
+                    continue
+                missing = sorted({c for unit in line for c in unit} - known)
+                if missing:
+                    logger.info("blocks: config line {} names chromosomes that are not loaded ({}), skipped".format(line, missing))
+                    lines.append([])
+                    continue
+                lines.append(line)
+            groups = blocks_mod.pair_list(lines)
+            logger.info("###Step: Blocks")
+            logger.info("homoeologous blocks of {} chromosome pairs (k = {}, 1 k-mer in {}, {}-bp windows)".format(
+                sum(map(len, groups)), self.block_k, 1 << self.block_sample, self.block_bin))
+            t0 = time.perf_counter()
+            lengths = [d_size[lab] for lab in labels]
+            res = blocks_mod.run(ctx, groups, labels, lengths, block_k=self.block_k, block_sample=self.block_sample,
+                                 bin_size=self.block_bin, min_votes=self.block_votes, max_gap=self.block_gap,
+                                 min_block=self.min_block)
+            tsv, link, fig = lay.out("blocks.tsv"), lay.out("block_link.txt"), lay.out("blocks." + self.figfmt)
+            with open(tsv, "w") as fout:
+                blocks_mod.write_tsv(fout, [p for group in res for p in group])
+            mk_ckp(lay.ckp(tsv))
+            with open(link, "w") as fout:
+                blocks_mod.write_links(fout, res)
+            mk_ckp(lay.ckp(link))
+            logger.info("blocks -> `{}` in {:.2f} s".format(os.path.basename(tsv), time.perf_counter() - t0))
+        except Exception as e:
+            logger.warning("blocks not written: {}".format(e))
+            try:
+                ctx.blocks_release()
+            except Exception:
+                pass
+            return
+        d_sg, sg_names, pal = dict(getattr(cl, "d_sg", None) or {}), list(getattr(cl, "sg_names", None) or []), getattr(self, "colors", None)
+
+        def done():      # on the main thread, with the other figures (see _write_matrix_in_background)
+            try:
+                from matplotlib import pyplot as plt
+                colors = pal.split(",") if isinstance(pal, str) else (pal or plt.rcParams["axes.prop_cycle"].by_key()["color"])
+                chrom_colors = {c: colors[sg_names.index(sg) % len(colors)] for c, sg in d_sg.items() if sg in sg_names}
+                blocks_mod.plot(fig, res, dict(zip(labels, lengths)), chrom_colors)
+                if os.path.exists(fig):
+                    mk_ckp(lay.ckp(fig))
+            except Exception as e:     # the figure is optional
+                logger.warning("blocks not plotted: {}".format(e))
+        self._background.append((fig, lambda: None, done))
+
     def run(self):
         self._background = []
         try:
@@ -569,6 +661,8 @@ class Pipeline:
             if self.custom_features is not None:
                 self._finish_background()      # `.kmer.mat` / sig-k-mer writers done: their threads would compete with the feature writers' 
                 self.stage_features(lay, cl, kmer_labels)
+            if not (self.disable_circos or self.disable_blocks):
+                self.stage_blocks(lay, labels, d_size, cl)
             if not (self.disable_ltr and self.disable_circos):
                 logger.info("Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
                             "outputs above, or pass -disable_ltr -disable_circos to silence this note")
