@@ -410,6 +410,20 @@ int sp_blocks_anchors(sp_ctx *ctx, int32_t *pos_a, int32_t *pos_b, uint8_t *opp,
 int sp_blocks_release(sp_ctx *ctx, int chrom);
 int sp_blocks_set_cells(sp_ctx *ctx, int cells);
 
+/* ---- LTR-pair alignment on the resident genome -------------------------------
+ * The similarity of an element's two LTRs, which the reference takes from whichever detector wrote the record
+ * (LTR.py:680-686): a global, banded alignment with linear gap costs, all integers, no traceback; the definition --
+ * band, column scores, tie order, the edge bit -- is in csrc/sp_ltralign.h.  Pair i is the left LTR
+ * [a_start[i], a_start[i] + a_len[i]) and the right LTR [b_start[i], b_start[i] + b_len[i]) of chromosome chrom[i],
+ * 0-based positions on the genome of sp_genome_add; `band` = w >= 0.  out: n x 6 int32, caller-owned: score, match,
+ * mismatch, gap, skip, flags.  Flag bits: 1 = the chosen path touched the first or last diagonal of the band (the
+ * result may be band-limited), 2 = the band |b_len - a_len| + 2 w + 1 is wider than SP_LA_MAXBAND = 1024, 4 = an LTR is
+ * longer than SP_LA_MAXLEN = 8192; a pair with bit 2 or 4 is not aligned and its other five columns are zero.
+ * SP_EINVAL: no genome loaded, a chromosome index out of range, a length below 1 or an interval off its chromosome,
+ * band < 0.  n = 0 is fine.  Pairs are handed to the device longest first.                                        */
+int sp_ltr_align(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *a_start, const int32_t *a_len,
+                 const int64_t *b_start, const int32_t *b_len, int band, int32_t *out);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

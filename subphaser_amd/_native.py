@@ -22,6 +22,8 @@ RANKTEST_MAX_GROUP = 64                            # SP_RT_MAXG in csrc/sp_rankt
 RANKTEST_WIDE_MAX_GROUP = 4096                     # SP_RW_MAXG in csrc/sp_rankwide.h
 RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: the `method` argument is the index
 BLOCKS_K_RANGE, BLOCKS_MAX_SAMPLE = (17, 31), 16   # SP_BK_KMIN, SP_BK_KMAX (odd only), SP_BK_SMAX in csrc/sp_blocks.h
+LTR_ALIGN_MAXLEN, LTR_ALIGN_MAXBAND = 8192, 1024    # SP_LA_MAXLEN, SP_LA_MAXBAND in csrc/sp_ltralign.h
+LTR_ALIGN_EDGE, LTR_ALIGN_BAND, LTR_ALIGN_LEN = 1, 2, 4   # SP_LA_F_*: the flag bits of ltr_align's last column
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
@@ -33,6 +35,7 @@ SYMBOLS = [
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
     "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_ranktest_wide", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
+    "sp_ltr_align",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -133,6 +136,7 @@ def load():
     L.sp_blocks_anchors.argtypes = [vp, vp, vp, vp, i64]
     L.sp_blocks_release.argtypes = [vp, ci]
     L.sp_blocks_set_cells.argtypes = [vp, ci]
+    L.sp_ltr_align.argtypes = [vp, i64, vp, vp, vp, vp, vp, ci, vp]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -956,6 +960,19 @@ class Context:
         """cells of the pair kernel's per-window table (a power of two, 2..4096): a small value sends small inputs through
         the band passes; results do not depend on it"""
         self._ck(self.L.sp_blocks_set_cells(self.h, int(cells)))
+
+    # -------------------------------------------------------------- LTR pairs
+    def ltr_align(self, chrom, a_start, a_len, b_start, b_len, band):
+        """Banded global alignment of LTR pairs on the resident genome (sp_ltr_align; definition in csrc/sp_ltralign.h):
+        int32 [n, 6] = score, match, mismatch, gap, skip, flags (LTR_ALIGN_EDGE / _BAND / _LEN).  Positions are 0-based."""
+        chrom = np.ascontiguousarray(chrom, np.int32)
+        a_start, b_start = np.ascontiguousarray(a_start, np.int64), np.ascontiguousarray(b_start, np.int64)
+        a_len, b_len = np.ascontiguousarray(a_len, np.int32), np.ascontiguousarray(b_len, np.int32)
+        n = chrom.size
+        assert a_start.size == a_len.size == b_start.size == b_len.size == n
+        out = np.zeros((n, 6), np.int32)
+        self._ck(self.L.sp_ltr_align(self.h, n, _p(chrom), _p(a_start), _p(a_len), _p(b_start), _p(b_len), int(band), _p(out)))
+        return out
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

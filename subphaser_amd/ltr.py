@@ -1,0 +1,238 @@
+"""The host side of the LTR stage: LTR-RT coordinates from a `.scn`, overlap resolution, identity, insertion ages.
+
+The reference detects LTR-RTs (ltr_finder, ltrharvest), writes them to `tmp/LTR.scn` -- its own checkpoint, which it
+re-reads with LTRHarvest (LTR.py:324-331, :609-701) -- classifies them with TEsorter, maps the subgenome-specific k-mers
+onto the elements, tests them for enrichment and dates the enriched ones from the similarity of their two LTRs
+(LTR.py:474-606, :680-686).  Here detection and classification are not run: the stage starts from the `.scn` a user
+supplies and uses every record of it, as the reference does under -all_ltr.  What this module restates is the record
+(fields, derived coordinates, id), the overlap resolution for records without a classification, the age arithmetic and
+the `.ltr.insert.data` / `.ltr.insert.summary` writers; the similarity is computed from the resident genome by
+Context.ltr_align (csrc/sp_ltralign.h) unless -ltr_identity scn asks for the file's."""
+import math
+
+import numpy as np
+
+from ._native import LTR_ALIGN_BAND as FLAG_BAND, LTR_ALIGN_EDGE as FLAG_EDGE, LTR_ALIGN_LEN as FLAG_LEN
+from .runtime import logger
+
+LTR_BAND = 64
+IDENTITY_MODES = ("align", "scn")
+MAX_OVL = 10
+
+
+class Record:
+    """One line of a `.scn` (LTRHarvestRecord, LTR.py:635-701): coordinates are 1-based, both ends included."""
+    __slots__ = ("start", "end", "element_len", "lltr", "rltr", "similarity", "seq_nr", "seq_id")
+
+    def __init__(self, fields, where=""):
+        if len(fields) == 11:
+            raise ValueError("{}: 11 columns: this is the raw ltrharvest format, whose 11th column is a sequence number; column 12, "
+                             "the sequence id, is missing (pass the `.scn` the reference's LTR step writes, e.g. tmp/LTR.scn, or "
+                             "append the id to every line)".format(where))
+        if len(fields) < 12:
+            raise ValueError("{}: unrecognized LTRHarvest format: {}".format(where, fields))
+        # s(ret) e(ret) l(ret) s(lLTR) e(lLTR) l(lLTR) s(rLTR) e(rLTR) l(rLTR) sim seq-nr chr: the reference takes the start
+        # from column 4 and the end from column 8
+        self.element_len, self.start, self.lltr = int(fields[2]), int(fields[3]), int(fields[5])
+        self.end, self.rltr = int(fields[7]), int(fields[8])
+        self.similarity, self.seq_nr, self.seq_id = float(fields[9]), int(fields[10]), fields[11]
+
+    @property
+    def lltr_e(self):
+        return self.start + self.lltr - 1
+
+    @property
+    def rltr_s(self):
+        return self.end - self.rltr + 1
+
+    @property
+    def key(self):
+        return (self.seq_id, self.start, self.end, self.lltr_e, self.rltr_s)
+
+    @property
+    def id(self):
+        return "{}:{}-{}:{}-{}".format(self.seq_id, self.start, self.end, self.lltr_e, self.rltr_s)
+
+    def overlap(self, other):
+        ovl = max(0, min(self.end, other.end) - max(self.start, other.start))
+        return 100 * ovl / (min(self.element_len, other.element_len))
+
+
+def read_scn(path):
+    """the records of a `.scn` in file order; `#` lines (and blank ones) are skipped, a trailing `#source` column is ignored"""
+    out = []
+    with open(path) as fh:
+        for ln, line in enumerate(fh, 1):
+            if line.startswith("#") or not line.strip():
+                continue
+            out.append(Record(line.strip().split(), "{}:{}".format(path, ln)))
+    return out
+
+
+def resolve_overlaps(ltrs, max_ovl=MAX_OVL):
+    """resolve_overlaps (LTR.py:422-468) for records of one sequence none of which is "completed": walking by start, of two
+    records that overlap by more than max_ovl % of the shorter the longer stays (the earlier on a tie) and is what the next
+    record is compared with; of two equal records the later goes.  What is returned is set(ltrs) - set(discards) with the
+    reference's equality -- the key (seq_id, start, end, lltr_e, rltr_s) -- so a discarded record takes every record of its
+    key with it.  Order: (start, end, lltr_e, rltr_s) (the reference leaves equal starts in set order)."""
+    last, discards = None, set()
+    for ltr in sorted(ltrs, key=lambda x: x.start):
+        if last is not None:
+            if ltr.key == last.key:
+                discard = ltr
+            elif ltr.overlap(last) > max_ovl:
+                discard = last if ltr.element_len > last.element_len else ltr
+            else:
+                last = ltr
+                continue
+            discards.add(discard.key)
+            if discard.key == ltr.key:
+                continue
+        last = ltr
+    seen, kept = set(discards), []
+    for ltr in ltrs:
+        if ltr.key not in seen:
+            seen.add(ltr.key)
+            kept.append(ltr)
+    return sorted(kept, key=lambda x: (x.start, x.end, x.lltr_e, x.rltr_s))
+
+
+def group_resolve_overlaps(ltrs):
+    """group_resolve_overlaps (LTR.py:415-420): runs of consecutive records of one sequence, each resolved on its own"""
+    out, i = [], 0
+    while i < len(ltrs):
+        j = i
+        while j < len(ltrs) and ltrs[j].seq_id == ltrs[i].seq_id:
+            j += 1
+        out += resolve_overlaps(ltrs[i:j])
+        i = j
+    return out
+
+
+def estimate_age(div, mu):
+    """estimate_age (LTR.py:680-686, JC69) of a divergence, in years"""
+    if div >= 0.75:
+        dist = div
+    else:
+        dist = -3 / 4 * math.log(1 - 4 * div / 3)
+    return dist / (mu * 2)
+
+
+def ltr_intervals(ltrs):
+    """0-based (a_start, a_len, b_start, b_len) of the two LTRs of every record"""
+    a0 = np.array([r.start - 1 for r in ltrs], np.int64)
+    la = np.array([r.lltr for r in ltrs], np.int64)
+    lb = np.array([r.rltr for r in ltrs], np.int64)
+    b0 = np.array([r.end - r.rltr for r in ltrs], np.int64)
+    return a0, la, b0, lb
+
+
+def divergences(ltrs, counts, mode):
+    """(div list, number of elements that fell back to the file's similarity).  counts: int32 [n, 6] of Context.ltr_align or
+    None.  align: mismatch / (match + mismatch) -- gap and skip columns carry no substitution information; an element
+    without a substitution column or one that was not aligned takes 1 - similarity / 100, which is what scn takes for all."""
+    divs, fell = [], 0
+    for i, r in enumerate(ltrs):
+        if mode == "align" and counts is not None:
+            m, x, flags = int(counts[i][1]), int(counts[i][2]), int(counts[i][5])
+            if m + x > 0 and not flags & (FLAG_BAND | FLAG_LEN):
+                divs.append(x / (m + x))
+                continue
+            fell += 1
+        divs.append(1 - r.similarity / 100)
+    return divs, fell
+
+
+def write_identity(fout, ltrs, counts, divs, ages):
+    fout.write("\t".join(["#id", "similarity", "score", "match", "mismatch", "gap", "skip", "flags", "div", "age"]) + "\n")
+    for i, r in enumerate(ltrs):
+        cc = ["NA"] * 6 if counts is None else [str(int(x)) for x in counts[i]]
+        fout.write("\t".join([r.id, str(r.similarity)] + cc + [str(divs[i]), str(ages[i])]) + "\n")
+
+
+def write_insert_data(fout, ltrs, ages, d_enriched, d_exchange, exclude_exchanges=False, non_specific=False):
+    """`.ltr.insert.data` as plot_insert_age writes it (LTR.py:474-511; `shared` is empty): ({sg: [age in Myr]}, enriched
+    records, number excluded as potential exchanges)"""
+    fout.write("\t".join(["ltr", "sg", "age"]) + "\n")
+    d_data, enriched, excluded = {}, [], 0
+    for ltr, age in zip(ltrs, ages):
+        if ltr.id in d_enriched:
+            sg = d_enriched[ltr.id]
+            enriched.append(ltr)
+            if exclude_exchanges and d_exchange.get(ltr.id) == "yes":
+                excluded += 1
+                continue
+        elif non_specific:
+            sg = "non-specific"
+        else:
+            continue
+        age = age / 1e6
+        fout.write("\t".join(map(str, [ltr.id, sg, age])) + "\n")
+        d_data.setdefault(sg, []).append(age)
+    return d_data, enriched, excluded
+
+
+def summary_ltr_time(d_data, fout):
+    """`.ltr.insert.summary` and the two log lines of summary_ltr_time (LTR.py:568-606): {sg: "median (95% CI)"}"""
+    fout.write("# Summary of LTR insertion age (million years)\n")
+    fout.write("\t".join(["#subgenome", "mean", "median", "standard_deviation", "75%-CI", "95%-CI", "99%-CI"]) + "\n")
+    d_info, xages, medians, lo95, hi95 = {}, [], [], [], []
+    for sg, ages in sorted(d_data.items()):
+        xages += ages
+        ages = np.array(ages)
+        median = np.median(ages)
+        medians.append(median)
+        t2_5, t97_5 = np.percentile(ages, 2.5), np.percentile(ages, 97.5)
+        lo95.append(t2_5)
+        hi95.append(t97_5)
+        ci95 = "{:.3f}-{:.3f}".format(abs(t2_5), t97_5)
+        ci99 = "{:.3f}-{:.3f}".format(abs(np.percentile(ages, 0.5)), np.percentile(ages, 99.5))
+        ci75 = "{:.3f}-{:.3f}".format(np.percentile(ages, 12.5), np.percentile(ages, 87.5))
+        median = "{:.3f}".format(median)
+        fout.write("\t".join([sg, "{:.3f}".format(ages.mean()), median, "{:.3f}".format(np.std(ages)), ci75, ci95, ci99]) + "\n")
+        d_info[sg] = "{} ({})".format(median, ci95)
+    logger.info("Summary of overall LTR insertion age (million years):")
+    logger.info("\tmedian: {:.3f}\t95% CI (percentile-based): {:.3f}-{:.3f}".format(
+        np.median(xages), abs(np.percentile(xages, 2.5)), np.percentile(xages, 97.5)))
+    logger.info("A rough estimation of the divergence–hybridization period: {:.3f}-{:.3f} ({:.3f})".format(
+        np.mean(hi95), np.mean(lo95), np.mean(medians)))
+    return d_info
+
+
+def _density(x, grid):
+    """Gaussian kernel density with R's default bandwidth (bw.nrd0), what geom_line(stat = "density") draws"""
+    x = np.asarray(x, float)
+    sd, iqr = (x.std(ddof=1) if x.size > 1 else 0.0), np.subtract(*np.percentile(x, [75, 25]))
+    lo = min(sd, iqr / 1.34) or sd or abs(x[0]) or 1.0
+    bw = 0.9 * lo * x.size ** -0.2
+    z = (grid[:, None] - x[None, :]) / bw
+    return np.exp(-0.5 * z * z).sum(axis=1) / (x.size * bw * math.sqrt(2 * math.pi))
+
+
+def plot(d_data, d_info, density_fig, histo_fig, sg_colors=None):
+    """`.ltr.insert.density.<figfmt>` and `.ltr.insert.histo.<figfmt>`: the two ggplot figures of plot_insert_age, drawn with
+    matplotlib (age density per subgenome; stacked histogram of 30 bins), annotated with the summary"""
+    import matplotlib
+    matplotlib.use("Agg")
+    from matplotlib import pyplot as plt
+    sgs = sorted(d_data)
+    cycle = plt.rcParams["axes.prop_cycle"].by_key()["color"]
+    colors = [(sg_colors or {}).get(sg, cycle[i % len(cycle)]) for i, sg in enumerate(sgs)]
+    text = "Summary: median (95% CI)\n" + "".join("{}: {}\n".format(sg, info) for sg, info in sorted(d_info.items()))
+    allx = np.concatenate([np.asarray(d_data[sg], float) for sg in sgs])
+    span = (allx.max() - allx.min()) or 1.0
+    grid = np.linspace(allx.min() - 0.1 * span, allx.max() + 0.1 * span, 512)
+    for kind, path in (("density", density_fig), ("histo", histo_fig)):
+        fig, ax = plt.subplots(figsize=(7, 7))
+        if kind == "density":
+            for sg, c in zip(sgs, colors):
+                ax.plot(grid, _density(d_data[sg], grid), color=c, lw=2, label=sg)
+            ax.set_ylabel("Density")
+        else:
+            ax.hist([d_data[sg] for sg in sgs], bins=30, stacked=True, color=colors, label=sgs)
+            ax.set_ylabel("Frequence")
+        ax.set_xlabel("LTR insertion age (million years)")
+        ax.text(0.97, 0.97, text, transform=ax.transAxes, ha="right", va="top")
+        ax.legend(loc="center right", frameon=False)
+        fig.savefig(path, dpi=300)
+        plt.close(fig)

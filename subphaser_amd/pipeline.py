@@ -13,8 +13,13 @@ Of modules 3-4 one step is here: the homoeologous blocks of the circos figure's 
 __main__.py:699-713).  The reference runs an aligner on every pair of homoeologous chromosomes; stage_blocks votes
 over the single-copy k-mers two chromosomes share, on the packed genome the map stage has just walked (blocks.py,
 csrc/sp_blocks.hip), and writes `blocks.tsv`, `block_link.txt` (the format of Circos.paf2blocks) and a figure.  It
-runs unless -just_core, -disable_circos or -disable_blocks is given; the LTR module and the circos figure itself
-stay with the reference.
+runs unless -just_core, -disable_circos or -disable_blocks is given.
+
+Of module 3 the part that needs no detector is here: stage_ltr takes LTR-RT coordinates from -ltr_scn (the `.scn` the
+reference's LTR step writes), maps the subgenome-specific k-mers onto the elements of the resident genome, writes
+`.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data` / `.summary` and the two age figures; the
+divergence of an element's two LTRs comes from a banded alignment on the device (ltr.py, csrc/sp_ltralign.hip).  LTR
+detection, TEsorter, the LTR trees and the circos figure itself stay with the reference.
 """
 import argparse
 import io
@@ -29,6 +34,7 @@ import numpy as np
 
 from . import REFERENCE_VERSION, __version__
 from . import blocks as blocks_mod
+from . import ltr as ltr_mod
 from . import circos, seqs, stats
 from .cluster import BOOTSTRAP_ENGINES, TEST_METHODS, Cluster
 from .config import SGConfig, check_duplicates, parse_idmap
@@ -93,7 +99,8 @@ CLI = [
         (("-just_core",), _FLAG),
     ]),
     ("LTR / Circos", "accepted for command-line compatibility; modules 3-4 stay with the reference, except the homoeologous "
-                     "blocks (-disable_blocks, -min_block, -alt_cfgs are used; see Blocks)",
+                     "blocks (-disable_blocks, -min_block, -alt_cfgs are used; see Blocks) and the LTR stage on given coordinates "
+                     "(-disable_ltr, -mu, -exclude_exchanges, -non_specific are used; see LTR)",
      [((o,), _STR) for o in ("-ltr_finder_options", "-ltr_harvest_options", "-tesorter_options", "-trimal_options",
                              "-tree_method", "-tree_options", "-ggtree_options", "-aligner", "-aligner_options",
                              "-chr_ordered")]
@@ -114,6 +121,18 @@ CLI = [
                                  help="anchors the winning cell of a window needs for the window to be called")),
         (("-block_gap",), dict(type=int, metavar="INT", default=blocks_mod.BLOCK_GAP,
                                help="windows a block may skip, and drift off its diagonal, between two called windows")),
+    ]),
+    ("LTR", "subgenome-specific LTR-RTs and their insertion ages from LTR-RT coordinates (the reference's module 3 without "
+            "detection, TEsorter and the LTR trees): the stage runs when -ltr_scn is given, unless -just_core or -disable_ltr; "
+            "every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured", [
+        (("-ltr_scn",), dict(type=str, metavar="FILE", default=None,
+                             help="LTR-RTs in the 12-column format of the reference's tmp/LTR.scn (ltrharvest's columns plus the "
+                                  "sequence id)")),
+        (("-ltr_identity",), dict(choices=list(ltr_mod.IDENTITY_MODES), default="align",
+                                  help="divergence of an element's two LTRs: align (banded global alignment on the GPU, "
+                                       "mismatch / (match + mismatch)) or scn (1 - similarity / 100 of the file, as the reference)")),
+        (("-ltr_band",), dict(type=int, metavar="INT", default=ltr_mod.LTR_BAND,
+                              help="diagonals either side of the band of the LTR alignment; provisional: judged on synthetic pairs only")),
     ]),
     ("Other options", None, [
         (("-p", "-ncpu"), dict(dest="ncpu", type=int, metavar="INT", default=NCPU)),
@@ -633,6 +652,117 @@ class Pipeline:
                 logger.warning("blocks not plotted: {}".format(e))
         self._background.append((fig, lambda: None, done))
 
+    # ---- stage 7: LTR-RTs from a .scn -------------------------------------------------------------------------
+    def stage_ltr(self, lay, labels, cl, kmer_labels):
+        """`.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data`, `.ltr.insert.summary` and the two age
+        figures from the LTR-RTs of -ltr_scn (step_ltr, __main__.py:549-620, without detection and classification)."""
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            logger.info("LTR stage skipped: it runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
+            return
+        logger.info("###Step: LTR")
+        ctx = get_context()
+        mode = getattr(self, "ltr_identity", "align")
+        band = int(getattr(self, "ltr_band", ltr_mod.LTR_BAND))
+        if band < 0:
+            raise ValueError("-ltr_band {} is below 0".format(band))
+        ltrs = ltr_mod.read_scn(self.ltr_scn)
+        logger.info("{} LTRs read from `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), self.ltr_scn))
+        aliases, index = dict(getattr(self, "d_targets", None) or {}), {lab: i for i, lab in enumerate(labels)}
+        known = []
+        for r in ltrs:
+            r.seq_id = aliases.get(r.seq_id, r.seq_id)
+            if r.seq_id in index:
+                known.append(r)
+        if len(known) < len(ltrs):
+            logger.info("{} LTRs lie on sequences that are not target chromosomes: skipped".format(len(ltrs) - len(known)))
+        lengths = [int(ctx.genome_len(i)) for i in range(len(labels))]
+        for r in known:
+            if not (1 <= r.start and r.lltr >= 1 and r.rltr >= 1 and r.lltr_e <= r.end and r.start <= r.rltr_s and r.end <= lengths[index[r.seq_id]]):
+                raise ValueError("{}: LTR-RT {} does not lie on its chromosome (length {}) or its LTRs (lengths {}, {}) do not lie in it".format(
+                    self.ltr_scn, r.id, lengths[index[r.seq_id]], r.lltr, r.rltr))
+        n_known = len(known)
+        ltrs = ltr_mod.group_resolve_overlaps(known)
+        logger.info("After filtering, {} / {} ({:.1%}) LTRs retained".format(len(ltrs), n_known, len(ltrs) / max(1, n_known)))
+        # map: the element is the reference's seq[start:end] -- the Python slice taken with the 1-based start
+        S, names = len(cl.sg_names), list(cl.sg_names)
+        chrom = np.array([index[r.seq_id] for r in ltrs], np.int32)
+        st, en = np.array([r.start for r in ltrs], np.int64), np.array([r.end for r in ltrs], np.int64)
+        if len(ltrs) and int((en - st).max()) > FEATURE_BIN:
+            raise ValueError("{}: an LTR-RT of {} bases is longer than a {}-base bin".format(self.ltr_scn, int((en - st).max()), FEATURE_BIN))
+        ctx.labels_set(kmer_labels.keys, kmer_labels.sg_idx, S)
+        counts = np.asarray(ctx.map_intervals(chrom, st, en), np.int64).reshape(len(ltrs), S) if len(ltrs) else np.zeros((0, S), np.int64)
+        hit = np.flatnonzero(counts.sum(axis=1) > 0).tolist()
+        ltr_map = lay.out("ltr.bin.count")
+        logger.info("Outputing `coordinate` - `LTR` maps to `{}`".format(ltr_map))
+        with open(ltr_map, "w") as fout:      # only mapped LTRs are output
+            fout.write("\t".join(["#chrom", "start", "end"] + names) + "\n")
+            for i in hit:
+                fout.write("{}\t0\t{}\t{}\n".format(ltrs[i].id, int(en[i] - st[i]), "\t".join(map(str, counts[i].tolist()))))
+        mk_ckp(lay.ckp(ltr_map))
+        logger.info("Processed {} sequences".format(len(ltrs)))
+        if len(ltrs) and len(kmer_labels.keys):
+            logger.info("{} ({:.2%}) sequences contain subgenome-specific kmers".format(len(hit), len(hit) / len(ltrs)))
+        logger.info("Enriching subgenome-specific LTR-RTs")
+        ltr_enrich = lay.out("ltr.enrich")
+        with open(ltr_enrich, "w") as fout:
+            d_enriched, d_exchange = stats.enrich_ltr(fout, cl.d_sg, counts[hit], colnames=names, rownames=[ltrs[i].id for i in hit],
+                                                      max_pval=self.max_pval, ctx=ctx)
+        mk_ckp(lay.ckp(ltr_enrich))
+        logger.info("Output: {}".format(ltr_enrich))
+        logger.info("{} significant subgenome-specific LTR-RTs".format(len(d_enriched)))
+        for sg, n in sorted(Counter(d_enriched.values()).items()):
+            logger.info("\t{} {}-specific LTR-RTs".format(n, sg))
+        # identity and ages
+        aligned = None
+        if not hasattr(ctx, "ltr_align"):
+            if mode == "align":
+                logger.info("this context has no ltr_align: -ltr_identity scn is used")
+                mode = "scn"
+        elif len(ltrs):
+            t0 = time.perf_counter()
+            a0, la, b0, lb = ltr_mod.ltr_intervals(ltrs)
+            aligned = np.asarray(ctx.ltr_align(chrom, a0, la, b0, lb, band))
+            logger.info("{} LTR pairs aligned (band {}) in {:.2f} s; {} touched the edge of their band".format(
+                len(ltrs), band, time.perf_counter() - t0, int((aligned[:, 5] & ltr_mod.FLAG_EDGE != 0).sum())))
+        divs, fell = ltr_mod.divergences(ltrs, aligned, mode)
+        if mode == "align" and fell:
+            logger.info("{} LTR pairs without an aligned substitution column or outside the limits of the alignment "
+                        "take the similarity of the file".format(fell))
+        ages = [ltr_mod.estimate_age(d, self.mu) for d in divs]
+        ident = lay.out("ltr.identity.tsv")
+        with open(ident, "w") as fout:
+            ltr_mod.write_identity(fout, ltrs, aligned, divs, ages)
+        mk_ckp(lay.ckp(ident))
+        if not d_enriched:
+            logger.warning("Because of none subgenome-specific LTR-RTs, plots of LTR-RTs are skipped.")
+            return
+        prefix = lay.out("ltr.insert")
+        with open(prefix + ".data", "w") as fout:
+            d_data, _, excluded = ltr_mod.write_insert_data(fout, ltrs, ages, d_enriched, d_exchange,
+                                                            exclude_exchanges=self.exclude_exchanges, non_specific=self.non_specific)
+        if self.exclude_exchanges:
+            logger.info("{} potentially exchanged LTR-RTs are excluded".format(excluded))
+        if not d_data:      # every enriched element was excluded as an exchange
+            logger.warning("no LTR-RT is left to date: `{}` and the plots are skipped".format(os.path.basename(prefix + ".summary")))
+            return
+        with open(prefix + ".summary", "w") as fout:
+            d_info = ltr_mod.summary_ltr_time(d_data, fout)
+        mk_ckp(lay.ckp(prefix + ".summary"))
+        figs = [prefix + ".density." + self.figfmt, prefix + ".histo." + self.figfmt]
+        sg_names, pal = list(cl.sg_names), getattr(self, "colors", None)
+
+        def done():      # on the main thread, with the other figures (see _write_matrix_in_background)
+            try:
+                colors = pal.split(",") if isinstance(pal, str) else pal
+                sg_colors = {sg: colors[i % len(colors)] for i, sg in enumerate(sg_names)} if colors else None
+                ltr_mod.plot(d_data, d_info, figs[0], figs[1], sg_colors)
+                for fig in figs:
+                    if os.path.exists(fig):
+                        mk_ckp(lay.ckp(fig))
+            except Exception as e:     # the figures are optional
+                logger.warning("LTR insertion ages not plotted: {}".format(e))
+        self._background.append((figs[0], lambda: None, done))
+
     def run(self):
         self._background = []
         try:
@@ -663,10 +793,15 @@ class Pipeline:
                 self.stage_features(lay, cl, kmer_labels)
             if not (self.disable_circos or self.disable_blocks):
                 self.stage_blocks(lay, labels, d_size, cl)
-            if not (self.disable_ltr and self.disable_circos):
+            ran_ltr = bool(getattr(self, "ltr_scn", None)) and not self.disable_ltr
+            if ran_ltr:
+                self.stage_ltr(lay, labels, cl, kmer_labels)
+            if ran_ltr:
+                logger.info("Of modules 3-4, LTR detection, TEsorter classification, the LTR trees and the circos figure are not "
+                            "part of this build; run the reference on the outputs above for them")
+            elif not (self.disable_ltr and self.disable_circos):
                 logger.info("Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
                             "outputs above, or pass -disable_ltr -disable_circos to silence this note")
-
 
 def main(argv=None):
     args = makeArgparse(argv)
