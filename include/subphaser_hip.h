@@ -427,7 +427,9 @@ int sp_ltr_align(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *a_
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);
-/* writes a JSON object {"kernel": {"calls": n, "ms": total}, ...} */
+/* writes a JSON object {"kernel": {"calls": n, "ms": total, "grid": g}, ...}; g: the largest grid (x * y * z
+ * workgroups) launched under that name while profiling was on, since sp_prof_reset -- the counting lanes' launches
+ * included */
 int sp_prof_report(sp_ctx *ctx, char *buf, int64_t cap);
 
 /* ---- bench support (not part of the reference's interface) --------------

@@ -346,11 +346,11 @@ int sp_blocks_index(sp_ctx *ctx, int chrom, int kb, int s, int64_t *n_sampled, i
         do {
             hipError_t e2 = hipMemsetAsync(p, 0xff, bytes, ctx->stream);
             if (e2 != hipSuccess) { rc = sp_fail(ctx, SP_EHIP, "sp_blocks_index: clearing the index failed: %s", hipGetErrorString(e2)); break; }
-            sp_prof_begin(ctx, "bk_build");
+            sp_prof_begin(ctx, "bk_build", dim3(bk_grid(ctx, n_units)));
             hipLaunchKernelGGL(bk_build, dim3(bk_grid(ctx, n_units)), dim3(SP_BK_THREADS), 0, ctx->stream, c.d_pk, c.d_pm, c.d_nm, n_units, kp, s,
                                x.d_keys, x.d_vals, x.cap, flags);
             sp_prof_end(ctx);
-            sp_prof_begin(ctx, "bk_singles");
+            sp_prof_begin(ctx, "bk_singles", dim3(bk_grid(ctx, cap)));
             hipLaunchKernelGGL(bk_singles, dim3(bk_grid(ctx, cap)), dim3(SP_BK_THREADS), 0, ctx->stream, x.d_vals, x.cap, flags);
             sp_prof_end(ctx);
             e2 = hipGetLastError();

@@ -216,6 +216,7 @@ struct sp_ctx {
     bool prof = false;
     std::vector<sp_prof_entry> prof_pending;
     std::map<std::string, std::pair<int64_t, double>> prof_acc;
+    std::map<std::string, int64_t> prof_grid;   // per kernel name: the largest grid (x * y * z workgroups) launched since sp_prof_reset
 };
 
 extern thread_local std::string g_sp_err;
@@ -227,7 +228,7 @@ int sp_buf_ensure(sp_ctx *ctx, sp_buf &b, int64_t bytes);
 void sp_buf_free(sp_buf &b);
 // does `p` point into this context's device memory (rows or a matrix staged earlier, read in place)?  Host pointers: false
 bool sp_on_device(sp_ctx *ctx, const void *p);
-void sp_prof_begin(sp_ctx *ctx, const char *name);
+void sp_prof_begin(sp_ctx *ctx, const char *name, dim3 grid);
 void sp_prof_end(sp_ctx *ctx);
 void sp_prof_flush(sp_ctx *ctx);
 
@@ -243,7 +244,7 @@ void sp_prof_flush(sp_ctx *ctx);
 // Launch wrapper: optional per-kernel event timing + launch error check.
 #define SP_LAUNCH(ctx, name, kernel, grid, block, shmem, ...)                       \
     do {                                                                            \
-        sp_prof_begin(ctx, name);                                                   \
+        sp_prof_begin(ctx, name, dim3(grid));                                       \
         hipLaunchKernelGGL(kernel, grid, block, shmem, (ctx)->stream, __VA_ARGS__); \
         sp_prof_end(ctx);                                                           \
         SP_HIP(ctx, hipGetLastError());                                             \

@@ -1547,6 +1547,7 @@ int sp_count_engine2(sp_ctx *ctx, sp_chrom &c, const sp_kparams &kp, int lower, 
     // (every block flushes its LDS histogram with one global atomic per non-empty bin: the sample runs on fewer blocks)
     const int64_t hist_blocks = exact ? (int64_t)ctx->n_cu * 2 : (int64_t)ctx->n_cu / 2;
     int grid_hist = (int)(hist_tiles < hist_blocks ? hist_tiles : hist_blocks);
+    if (grid_hist < 1) grid_hist = 1;      // (n_cu / 2 is no block on a device of one compute unit)
     if (sh_hist > 48 * 1024)
         SP_HIP(ctx, hipFuncSetAttribute((const void *)c2_hist_fine, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sh_hist));
     SP_LAUNCH(ctx, exact ? "c2_hist_fine" : "c2_hist_sample", c2_hist_fine, dim3(grid_hist), dim3(C2_P1_THREADS), sh_hist,

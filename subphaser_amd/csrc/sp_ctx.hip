@@ -2,6 +2,7 @@
 #include <stdarg.h>
 
 #include "sp_common.h"
+#include "sp_culimit.h"
 #include "sp_internal.h"
 
 thread_local std::string g_sp_err;
@@ -58,8 +59,13 @@ void sp_buf_free(sp_buf &b) {
     b.cap = 0;
 }
 
-void sp_prof_begin(sp_ctx *ctx, const char *name) {
+void sp_prof_begin(sp_ctx *ctx, const char *name, dim3 grid) {
     if (!ctx->prof) return;
+    // the largest grid of this name since sp_prof_reset: kept at the launch, whichever stream (a counting lane's
+    // included) ctx->stream is bound to
+    int64_t &most = ctx->prof_grid[name];
+    const int64_t blocks = (int64_t)grid.x * grid.y * grid.z;
+    if (blocks > most) most = blocks;
     sp_prof_entry e;
     e.name = name;
     hipEventCreate(&e.e0);
@@ -105,7 +111,8 @@ int sp_ctx_create(int device, void *stream, sp_ctx **out) {
     SP_HIP(ctx, hipSetDevice(device));
     hipDeviceProp_t prop;
     SP_HIP(ctx, hipGetDeviceProperties(&prop, device));
-    ctx->n_cu = prop.multiProcessorCount;
+    // SP_CU_LIMIT (sp_culimit.h): reckon with fewer compute units, read here and nowhere else
+    ctx->n_cu = sp_cu_limit(getenv("SP_CU_LIMIT"), prop.multiProcessorCount);
     if (stream) {
         ctx->stream = (hipStream_t)stream;
     } else {
@@ -417,6 +424,7 @@ int sp_prof_reset(sp_ctx *ctx) {
     if (!ctx) return SP_EINVAL;
     sp_prof_flush(ctx);
     ctx->prof_acc.clear();
+    ctx->prof_grid.clear();
     return SP_OK;
 }
 int sp_prof_report(sp_ctx *ctx, char *buf, int64_t cap) {
@@ -426,8 +434,10 @@ int sp_prof_report(sp_ctx *ctx, char *buf, int64_t cap) {
     bool first = true;
     for (auto &kv : ctx->prof_acc) {
         char tmp[256];
-        snprintf(tmp, sizeof tmp, "%s\"%s\": {\"calls\": %lld, \"ms\": %.6f}", first ? "" : ", ",
-                 kv.first.c_str(), (long long)kv.second.first, kv.second.second);
+        const auto g = ctx->prof_grid.find(kv.first);
+        snprintf(tmp, sizeof tmp, "%s\"%s\": {\"calls\": %lld, \"ms\": %.6f, \"grid\": %lld}", first ? "" : ", ",
+                 kv.first.c_str(), (long long)kv.second.first, kv.second.second,
+                 (long long)(g == ctx->prof_grid.end() ? 0 : g->second));
         s += tmp;
         first = false;
     }
