@@ -166,7 +166,9 @@ int sp_filter_hist(sp_ctx *ctx, uint64_t *tot, int64_t cap);
  * where chunk(s) reproduces the reference's 10-Mb chunking (Seqs.py:121-139;
  * chunk_size = 0 disables it), so that a bin straddling a chunk boundary is
  * reported on two lines like the reference does.
- * slot_counts: nslots x n_sg int32 (overwritten).                          */
+ * slot_counts: nslots x n_sg int32 (overwritten).
+ * A label set belongs to the k it was set at: after an sp_count with another k (or an sp_labels_set that failed)
+ * the map entries and sp_labels_hit return SP_EINVAL until sp_labels_set succeeds again.  */
 int sp_labels_set(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, int n_sg);
 /* the same with `keys` and `sg` already in DEVICE memory (e.g. the rows Cluster.output_kmers selected, kept where
  * sp_kmer_ttest tested them: Cluster.py:186-194 hands the reference's d_kmers dict to Seqs.map_kmer3 in memory too):

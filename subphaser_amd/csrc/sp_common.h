@@ -12,6 +12,7 @@
 
 #include "../../include/subphaser_hip.h"
 #include "sp_carve.h"
+#include "sp_labelplan.h"
 
 #define SP_WAVE 64
 
@@ -85,6 +86,16 @@ struct sp_tabref {
 
 struct sp_blocks_state;   // sp_blocks.hip
 
+// The label set of sp_labels_set: `kind` says which buffers hold it (sp_labelplan.h), bb / ovf_mask describe a bucket
+// table.  `ready` is cleared on entry to the table build and by sp_count whenever k changes, and set only when
+// sp_labels_set returns SP_OK: the map entries refuse to run without it.
+struct sp_label_state {
+    sp_label_kind kind = SP_LABELS_DIRECT;
+    int bb = 0;                  // bucket bits of the compact / quad-bucket table (both live in b_ctab / b_covf), else 0
+    uint64_t ovf_mask = 0;       // entries of its overflow table - 1
+    bool ready = false;
+};
+
 struct sp_prof_entry {
     std::string name;
     hipEvent_t e0, e1;
@@ -135,12 +146,7 @@ struct sp_ctx {
     int64_t bloom_last_n = -1;   // label count and size of the pair filter sp_map_filter_build chose last (same count: same size, no fill check)
     int bloom_last_bits = 0, bloom_last_k = 0;
     sp_buf b_ctab, b_covf;       // compact pair table (S <= 3: buckets of two tagged entries) and its overflow table (sp_map.h)
-    int ct_bb = 0;               // bucket bits of the compact table the current label set lives in (0: the direct table)
-    uint32_t ct_ovf_mask = 0;
-    int sq_bb = 0;               // k > 15: bucket bits of the quad-bucket table (sp_sparse.hip; lives in b_ctab / b_covf), 0: hash table
-    uint64_t sq_ovf_mask = 0;
-    int map_engine = 0;          // 0 = pair table (S <= 7), 1 = label table
-    bool labels_ready = false;
+    sp_label_state labels;       // the table the current label set lives in, and whether the map entries may use it
     uint32_t *d_bloom = nullptr; // L2-resident pair filter over hashed (k-1)-mers (sp_map.hip), 2^bloom_bits bits
     int bloom_bits = 0;
     int n_sg = 0;

@@ -31,7 +31,8 @@ int sp_count_engine3_batch(sp_ctx *ctx, const int *chrom_idx, int n, const sp_kp
 void sp_sparse_release(sp_ctx *ctx);
 int sp_sparse_count(sp_ctx *ctx, int k, int lower);
 int sp_sparse_dump(sp_ctx *ctx, int chrom, uint64_t *keys, uint32_t *counts);
-int sp_sparse_labels_set(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, bool on_device);
+int sp_sparse_labels_build(sp_ctx *ctx, const sp_label_plan &plan, const unsigned long long *d_keys, const uint8_t *d_sg,
+                           int64_t n, unsigned long long *d_flags);
 int sp_sparse_map_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n);
 int sp_sparse_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
                           const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts);

@@ -69,8 +69,6 @@ __device__ __forceinline__ void map_pair_scan(const uint32_t *__restrict__ pk, c
     });
 }
 
-#define MAP_PAIR_MAX_SG 7
-
 struct map_pair_loc {
     uint32_t idx;   // canonical (k-1)-mer
     int field;
@@ -118,7 +116,7 @@ __host__ __device__ __forceinline__ map_pair_loc map_pair_loc_suffix(uint64_t o,
 #define MAP_CT_ANY 0x6DB6DBu          // the label bits of all eight fields
 #define MAP_CT_PAYLOAD 0xFFFFFFu
 #define MAP_CT_OVF (1u << 24)
-#define MAP_CT_MAX_TAG_BITS 2         // bits of mix(t) in the tag (next to side and e)
+// (MAP_CT_MAX_TAG_BITS, the bits of mix(t) in the tag next to side and e: sp_labelplan.h, the sizing needs it)
 struct map_ptab {
     uint32_t *direct;                 // 4^(k-1) words, 4-bit fields (S <= 7), or NULL
     uint4 *buckets;                   // compact table: four entries per bucket
@@ -216,6 +214,11 @@ __host__ __device__ __forceinline__ int map_ct_sites(uint64_t o, int k, map_ct_s
                         // 512 x 4 (8 per SIMD, 64 VGPRs) 32.6, 256 x 8 33.0, 384 x 5 35.4, 1024 x 2 33.6
 #endif
 #define MAP_RANGE (MAP_BLOCK * SP_UNIT)  // starts per block iteration
+// the grid of every map walk, k <= 15 and k > 15: a workgroup per range of MAP_BLOCK units, MAP_GRID_MULT per compute unit at most
+inline int64_t map_grid(const sp_ctx *ctx, int64_t n_ranges) {
+    const int64_t cap = (int64_t)ctx->n_cu * MAP_GRID_MULT;
+    return n_ranges < cap ? n_ranges : cap;
+}
 // ---- LDS of the two-phase walks over a unit (map_unit_scan64 in sp_map.hip, map_unit_scan64_h in sp_sparse.hip)
 #ifndef MAP2_P2
 #define MAP2_P2 1      // queue entries per lane and iteration of the candidate phase (2: 34.5 against 34.3 ms -- the wait is not per wave)

@@ -595,37 +595,36 @@ k5_map_mask2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, c
     }
 }
 
-// the exact pair table the current label set lives in (compact when ctx->ct_bb != 0)
+// the exact pair table the current label set lives in (SP_LABELS_DIRECT or SP_LABELS_COMPACT)
 static map_ptab map_ptab_of(const sp_ctx *ctx) {
+    const bool compact = ctx->labels.kind == SP_LABELS_COMPACT;
     map_ptab T;
-    T.direct = ctx->ct_bb ? nullptr : (uint32_t *)ctx->b_ptab.p;
-    T.buckets = ctx->ct_bb ? (uint4 *)ctx->b_ctab.p : nullptr;
+    T.direct = compact ? nullptr : (uint32_t *)ctx->b_ptab.p;
+    T.buckets = compact ? (uint4 *)ctx->b_ctab.p : nullptr;
     T.ovf = (unsigned long long *)ctx->b_covf.p;
-    T.ovf_mask = ctx->ct_ovf_mask;
+    T.ovf_mask = (uint32_t)ctx->labels.ovf_mask;
     T.sb = 2 * (ctx->k - 3);
-    T.tb = ctx->ct_bb ? T.sb - ctx->ct_bb : 0;
+    T.tb = compact ? T.sb - ctx->labels.bb : 0;
     return T;
 }
 
-// descriptors of the chromosomes [first, first + n) -> device, then the one launch
-static int map_launch_dense(sp_ctx *ctx, const std::vector<map_chrom_desc> &hd, int64_t n_ranges, const sp_map_params &P) {
-    if (n_ranges <= 0) return SP_OK;
-    int rcb = sp_buf_ensure(ctx, ctx->b_mapdesc, (int64_t)(hd.size() * sizeof(map_chrom_desc)));
-    if (rcb) return rcb;
-    // (pageable source: hipMemcpyAsync returns once the runtime has staged it, `hd` may die afterwards)
-    SP_HIP(ctx, hipMemcpyAsync(ctx->b_mapdesc.p, hd.data(), hd.size() * sizeof(map_chrom_desc), hipMemcpyHostToDevice,
-                              ctx->stream));
-    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
-    int64_t grid = n_ranges;
-    if (grid > (int64_t)ctx->n_cu * MAP_GRID_MULT) grid = (int64_t)ctx->n_cu * MAP_GRID_MULT;
-    const map_ptab T = map_ptab_of(ctx);
-    if (T.buckets)
-        SP_LAUNCH(ctx, "k5_map", k5_map2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
-                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
-    else
-        SP_LAUNCH(ctx, "k5_map", k5_map2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
-                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
-    return SP_OK;
+// the parameters of a bins walk; its LDS histogram serves when the slots a range of MAP_RANGE starts touches fit it
+static sp_map_params map_params_of(int64_t len, int64_t bin_size, int64_t chunk_size, int64_t nslots, int S) {
+    sp_map_params P;
+    P.n_units = (len + SP_UNIT - 1) / SP_UNIT;
+    P.bin_size = bin_size;
+    P.chunk_size = chunk_size;
+    P.nslots = nslots;
+    P.S = S;
+    const int64_t local = MAP_RANGE / bin_size + 3 + (chunk_size > 0 ? MAP_RANGE / chunk_size + 2 : 0);
+    P.use_lds = (local * S <= MAP_LDS_ENTRIES) ? 1 : 0;
+    return P;
+}
+
+// the one readiness test of the map entries (sp_label_state in sp_common.h says when `ready` holds)
+static int map_need_labels(sp_ctx *ctx, const char *entry) {
+    if (ctx->labels.ready) return SP_OK;
+    return sp_fail(ctx, SP_EINVAL, "%s: call sp_labels_set first", entry);
 }
 
 // K5, label-table engine (any S <= 126; the rolling scan + one byte gather per candidate start)
@@ -966,6 +965,164 @@ int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n
     return SP_OK;
 }
 
+// ----------------------------------------------------------------- one dispatch per walk mode
+// Each switches on the kind of table the label set lives in; the k > 15 kinds go on to sp_sparse.hip, beside their kernels.
+
+// bins mode, pair-table kinds: the descriptors of the queued chromosomes -> device, then the one launch
+static int map_bins_flush(sp_ctx *ctx, const std::vector<map_chrom_desc> &hd, int64_t n_ranges, const sp_map_params &P) {
+    if (n_ranges <= 0) return SP_OK;
+    int rcb = sp_buf_ensure(ctx, ctx->b_mapdesc, (int64_t)(hd.size() * sizeof(map_chrom_desc)));
+    if (rcb) return rcb;
+    // (pageable source: hipMemcpyAsync returns once the runtime has staged it, `hd` may die afterwards)
+    SP_HIP(ctx, hipMemcpyAsync(ctx->b_mapdesc.p, hd.data(), hd.size() * sizeof(map_chrom_desc), hipMemcpyHostToDevice,
+                              ctx->stream));
+    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
+    const int64_t grid = map_grid(ctx, n_ranges);
+    const map_ptab T = map_ptab_of(ctx);
+    if (T.buckets)
+        SP_LAUNCH(ctx, "k5_map", k5_map2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
+                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
+    else
+        SP_LAUNCH(ctx, "k5_map", k5_map2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
+                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
+    return SP_OK;
+}
+
+// bins mode, one chromosome: the pair-table kinds queue it in `hd` (every chromosome in ONE launch: map_bins_flush), the
+// other kinds launch here
+static int map_bins_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n,
+                           std::vector<map_chrom_desc> &hd, int64_t &hd_ranges) {
+    if (P.n_units == 0) return SP_OK;
+    const int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
+    switch (ctx->labels.kind) {
+    case SP_LABELS_DIRECT:
+    case SP_LABELS_COMPACT:
+        hd.push_back(map_chrom_desc{c.d_pk, c.d_pm, c.d_nm, P.n_units, P.nslots, hd_ranges, d_counts, d_n});
+        hd_ranges += n_ranges;
+        return SP_OK;
+    case SP_LABELS_LABEL_BYTES:
+        SP_LAUNCH(ctx, "k5_map_lab", k5_map_lab, dim3((unsigned)map_grid(ctx, n_ranges)), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
+                  sp_make_kparams32(ctx->k), P, ctx->d_label, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+        return SP_OK;
+    default:
+        return sp_sparse_map_launch(ctx, c, P, d_counts, d_n);
+    }
+}
+
+// feature mode: one packed sequence of features
+static int map_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
+                           const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts) {
+    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
+    const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_COMPACT:
+        SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm, kp, n_units,
+                  d_foff, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    case SP_LABELS_DIRECT:
+        SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm, kp, n_units,
+                  d_foff, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    case SP_LABELS_LABEL_BYTES:
+        SP_LAUNCH(ctx, "k5_map_feat_lab", k5_map_feat_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp, n_units,
+                  d_foff, n_feat, S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    default:
+        return sp_sparse_feat_launch(ctx, d_pk, d_pm, d_nm, n_units, d_foff, n_feat, S, d_counts);
+    }
+}
+
+// interval mode: the per-unit subgenome masks of one chromosome
+static int map_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, const unsigned long long *d_cov,
+                           unsigned long long *d_masks) {
+    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
+    const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_COMPACT:
+        SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp,
+                  n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        return SP_OK;
+    case SP_LABELS_DIRECT:
+        SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp,
+                  n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        return SP_OK;
+    case SP_LABELS_LABEL_BYTES:
+        SP_LAUNCH(ctx, "k5_map_mask_lab", k5_map_mask_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, n_units,
+                  S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        return SP_OK;
+    default:
+        return sp_sparse_mask_launch(ctx, c, n_units, S, d_cov, d_masks);
+    }
+}
+
+// the labelled k-mers a walk has marked "seen"
+static int map_hit_launch(sp_ctx *ctx, unsigned long long *d_n) {
+    const unsigned long long *d_keys = (const unsigned long long *)ctx->b_labkeys.p;
+    switch (ctx->labels.kind) {
+    case SP_LABELS_COMPACT:
+        if (ctx->n_labels > 0)
+            SP_LAUNCH(ctx, "k4_ctab_seen", k4_ctab_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0, d_keys, ctx->n_labels,
+                      ctx->k, map_ptab_of(ctx), d_n);
+        return SP_OK;
+    case SP_LABELS_DIRECT:
+        if (ctx->n_labels > 0)
+            SP_LAUNCH(ctx, "k4_pair_seen", k4_pair_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0, d_keys, ctx->n_labels,
+                      ctx->k, (const uint32_t *)ctx->b_ptab.p, d_n);
+        return SP_OK;
+    case SP_LABELS_LABEL_BYTES:
+        SP_LAUNCH(ctx, "k4_count_seen", k4_count_seen, dim3((unsigned)(ctx->n_cu * 8)), dim3(256), 0,
+                  (const uint8_t *)ctx->d_label, ctx->nslots, d_n);
+        return SP_OK;
+    default:
+        return sp_sparse_hit(ctx, d_n);
+    }
+}
+
+// ----------------------------------------------------------------- sp_labels_set
+// k <= 15: the planned table from the staged keys.  `table_clean`: the direct table holds nothing (its previous set was
+// un-built key by key).
+static int labels_build_dense(sp_ctx *ctx, const sp_label_plan &plan, const unsigned long long *d_keys, const uint8_t *d_sg,
+                              int64_t n, bool table_clean, unsigned long long *d_flags) {
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    int rc;
+    switch (plan.kind) {
+    case SP_LABELS_COMPACT:
+        if ((rc = sp_buf_ensure(ctx, ctx->b_ctab, plan.bucket_bytes))) return rc;
+        if ((rc = sp_buf_ensure(ctx, ctx->b_covf, plan.ovf_bytes))) return rc;
+        SP_HIP(ctx, hipMemsetAsync(ctx->b_ctab.p, 0, (size_t)plan.bucket_bytes, ctx->stream));
+        SP_HIP(ctx, hipMemsetAsync(ctx->b_covf.p, 0, (size_t)plan.ovf_bytes, ctx->stream));
+        if (n > 0)      // d_flags[2] = overflow table full, [3] = keys in the overflow table
+            SP_LAUNCH(ctx, "k4_ctab_build", k4_ctab_build, dim3(grid), dim3(256), 0, d_keys, d_sg, n, ctx->k, map_ptab_of(ctx),
+                      d_flags + 2);
+        return SP_OK;
+    case SP_LABELS_DIRECT:
+        if ((rc = sp_buf_ensure(ctx, ctx->b_ptab, plan.entries * 4))) return rc;
+        if (!table_clean) SP_HIP(ctx, hipMemsetAsync(ctx->b_ptab.p, 0, (size_t)plan.entries * 4, ctx->stream));
+        if (n > 0)
+            SP_LAUNCH(ctx, "k4_pair_table", k4_pair_table, dim3(grid), dim3(256), 0, d_keys, d_sg, n, ctx->k,
+                      (uint32_t *)ctx->b_ptab.p);
+        ctx->ptab_k = ctx->k;
+        ctx->ptab_n = n;
+        return SP_OK;
+    default:      // SP_LABELS_LABEL_BYTES
+        if (!ctx->d_label) SP_HIP(ctx, hipMalloc(&ctx->d_label, (size_t)ctx->nslots));
+        SP_HIP(ctx, hipMemsetAsync(ctx->d_label, 0, (size_t)ctx->nslots, ctx->stream));
+        if (n > 0)
+            SP_LAUNCH(ctx, "k4_labels", k4_labels, dim3(grid), dim3(256), 0, d_keys, d_sg, n, sp_make_kparams(ctx->k), ctx->d_label);
+        return SP_OK;
+    }
+}
+
+// the plan becomes the context's label state (not ready yet), then its table is built
+static int labels_build(sp_ctx *ctx, const sp_label_plan &plan, const unsigned long long *d_keys, const uint8_t *d_sg, int64_t n,
+                        bool table_clean, unsigned long long *d_flags) {
+    ctx->labels.kind = plan.kind;
+    ctx->labels.bb = plan.bb;
+    ctx->labels.ovf_mask = plan.ovf_n ? (uint64_t)(plan.ovf_n - 1) : 0;
+    return ctx->sparse_mode ? sp_sparse_labels_build(ctx, plan, d_keys, d_sg, n, d_flags)
+                            : labels_build_dense(ctx, plan, d_keys, d_sg, n, table_clean, d_flags);
+}
+
 extern "C" {
 
 static int labels_set_impl(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, int n_sg, bool on_device) {
@@ -974,76 +1131,39 @@ static int labels_set_impl(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg,
     if (ctx->k <= 0 || (ctx->nslots <= 0 && !ctx->sparse_mode))
         return sp_fail(ctx, SP_EINVAL, "sp_labels_set: call sp_count first (it fixes k)");
     SP_HIP(ctx, hipSetDevice(ctx->device));
-    // device flags of this call: [0] largest label (device hand-over), [2] compact table: overflow table full,
-    // [3] keys in the overflow table.  Read back ONCE, at the end.
-    int rcfl = sp_buf_ensure(ctx, ctx->b_lflags, 64);
-    if (rcfl) return rcfl;
+    // device flags of this call: [0] largest label (device hand-over), [2] bucket table: overflow table full,
+    // [3] keys in the overflow table.  They reach the host through k4_flags_out.
+    int rc = sp_buf_ensure(ctx, ctx->b_lflags, 64);
+    if (rc) return rc;
     unsigned long long *d_flags = (unsigned long long *)ctx->b_lflags.p;
+    if (!ctx->h_lflags) SP_HIP(ctx, hipHostMalloc((void **)&ctx->h_lflags, 64, hipHostMallocDefault));
     SP_HIP(ctx, hipMemsetAsync(d_flags, 0, 64, ctx->stream));
+    auto flags_out = [&]() -> int {
+        SP_LAUNCH(ctx, "k4_flags_out", k4_flags_out, dim3(1), dim3(64), 0, (const unsigned long long *)d_flags, ctx->h_lflags);
+        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
+        if (on_device && n > 0 && (int)(unsigned int)ctx->h_lflags[0] >= n_sg)
+            return sp_fail(ctx, SP_EINVAL, "sp_labels_set: label %d >= n_sg %d", (int)(unsigned int)ctx->h_lflags[0], n_sg);
+        return SP_OK;
+    };
+    // the largest label is checked BEFORE any table is touched: a bad set must leave the previous one intact -- and must
+    // not leave labels >= n_sg in the hashed tables of k > 15.  Labels handed over in device memory cost one more round
+    // trip of the 64-byte flag block for that (~20 us).
     if (on_device && n > 0) {
         SP_LAUNCH(ctx, "k4_label_max", k4_label_max, dim3((unsigned)(n < 65536 ? 1 : ctx->n_cu)), dim3(256), 0, sg, n, (unsigned int *)d_flags);
+        if ((rc = flags_out())) return rc;
     } else {
         uint8_t mx = 0;     // (a reduction the compiler vectorises; an early-exit loop over 2 M labels took 1 ms)
         for (int64_t i = 0; i < n; i++) mx = sg[i] > mx ? sg[i] : mx;
         if (n > 0 && mx >= n_sg) return sp_fail(ctx, SP_EINVAL, "sp_labels_set: label %d >= n_sg %d", (int)mx, n_sg);
     }
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    if (!ctx->h_lflags) SP_HIP(ctx, hipHostMalloc((void **)&ctx->h_lflags, 64, hipHostMallocDefault));
-    if (on_device && n > 0) {
-        // the labels are checked BEFORE any table is touched (one more round trip of a 64-byte flag block, ~20 us): a
-        // bad hand-over must leave the previous label set intact -- and must not leave labels >= n_sg in the hashed
-        // table of the k > 15 engine (advisor r04)
-        SP_LAUNCH(ctx, "k4_flags_out", k4_flags_out, dim3(1), dim3(64), 0, (const unsigned long long *)d_flags, ctx->h_lflags);
-        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if ((int)(unsigned int)ctx->h_lflags[0] >= n_sg)
-            return sp_fail(ctx, SP_EINVAL, "sp_labels_set: label %d >= n_sg %d", (int)(unsigned int)ctx->h_lflags[0], n_sg);
-    }
-    auto label_check = [&]() -> int {      // after k4_flags_out and a synchronisation of the stream
-        if (!(on_device && n > 0)) return SP_OK;
-        const unsigned long long hf = ctx->h_lflags[0];
-        if ((int)(unsigned int)hf >= n_sg) {
-            ctx->labels_ready = false;
-            return sp_fail(ctx, SP_EINVAL, "sp_labels_set: label %d >= n_sg %d", (int)(unsigned int)hf, n_sg);
-        }
-        return SP_OK;
-    };
-    if (ctx->sparse_mode) {
-        ctx->n_sg = n_sg;
-        ctx->n_labels = n;
-        int rcs = sp_sparse_labels_set(ctx, keys, sg, n, on_device);
-        if (rcs) return rcs;
-        SP_LAUNCH(ctx, "k4_flags_out", k4_flags_out, dim3(1), dim3(64), 0, (const unsigned long long *)d_flags, ctx->h_lflags);
-        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        return label_check();
-    }
-    const char *eng = getenv("SP_MAP_ENGINE");
-    ctx->map_engine = (n_sg > MAP_PAIR_MAX_SG || (eng && eng[0] == '1')) ? 1 : 0;
+    sp_label_plan plan = sp_label_plan_make(ctx->k, n, n_sg, ctx->nslots, sp_label_env_read());
+    ctx->labels.ready = false;
     ctx->n_sg = n_sg;
-    ctx->labels_ready = false;
-    const int64_t entries = 1LL << (2 * (ctx->k - 1));
-    // Compact table (sp_map.h) when the labels fit 2-bit fields, the direct table is beyond every cache and the
-    // compact one is at least four times smaller: 2^bb buckets of four entries, bb >= log2(SP_CTAB_FACTOR (default 2) x n)
-    // -- a labelled k-mer brings ~3.6 keys (two (k-1)-mers, each under two (k-3)-mers, shared with its neighbours in
-    // a run) -- and at most 2 bits of the mixed (k-3)-mer in the tag.
-    ctx->ct_bb = 0;
-    bool compact = false;
-    int bb = 8;
-    {
-        const char *env_ct = getenv("SP_CTAB");           // "0": never (cross-check), "1": whenever the tag fits
-        const char *env_f = getenv("SP_CTAB_FACTOR");
-        const int64_t factor = env_f && atoll(env_f) > 0 ? atoll(env_f) : 2;
-        const int sb = 2 * (ctx->k - 3);
-        while (bb < 30 && ((int64_t)1 << bb) < factor * (n > 0 ? n : 1)) bb++;
-        if (bb < sb - MAP_CT_MAX_TAG_BITS) bb = sb - MAP_CT_MAX_TAG_BITS;
-        const bool fits = ctx->map_engine == 0 && n_sg <= 3 && ctx->k >= 5 && bb >= 1 && bb <= sb && bb <= 27;
-        const bool forced = env_ct && env_ct[0] == '1';
-        compact = fits && !(env_ct && env_ct[0] == '0') &&
-                  (forced || (entries * 4 > (64LL << 20) && ((int64_t)16 << bb) * 4 <= entries * 4));
-    }
+    ctx->n_labels = n;
     // direct table: the previous label set (same k, same buffer) is un-built key by key instead of memset -- while its
     // keys are still in b_labkeys
     bool table_clean = false;
-    if (!compact && ctx->map_engine == 0 && ctx->ptab_k == ctx->k && ctx->b_ptab.p && ctx->b_ptab.cap >= entries * 4) {
+    if (plan.kind == SP_LABELS_DIRECT && ctx->ptab_k == ctx->k && ctx->b_ptab.p && ctx->b_ptab.cap >= plan.entries * 4) {
         if (ctx->ptab_n > 0)
             SP_LAUNCH(ctx, "k4_pair_clear", k4_pair_clear, dim3((unsigned)((ctx->ptab_n + 255) / 256)), dim3(256), 0,
                       (const unsigned long long *)ctx->b_labkeys.p, ctx->ptab_n, ctx->k, (uint32_t *)ctx->b_ptab.p);
@@ -1051,74 +1171,34 @@ static int labels_set_impl(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg,
     }
     ctx->ptab_k = 0;      // (from here on the direct table is in an unknown state unless it is rebuilt below)
     ctx->ptab_n = 0;
-    ctx->n_labels = n;
-    int rcb = sp_buf_ensure(ctx, ctx->b_labkeys, (n > 0 ? n : 1) * 9);
-    if (rcb) return rcb;
+    // the labelled keys stay on the device: the filter is built from them, sp_labels_hit walks them, the next call un-builds
+    // the direct table with them
+    const int64_t n1 = n > 0 ? n : 1;
+    if ((rc = sp_buf_ensure(ctx, ctx->b_labkeys, n1 * 9 + 64))) return rc;
     unsigned long long *d_keys = (unsigned long long *)ctx->b_labkeys.p;
-    uint8_t *d_sg = (uint8_t *)(d_keys + (n > 0 ? n : 1));
+    uint8_t *d_sg = (uint8_t *)(d_keys + n1);
     if (n > 0 && (const void *)keys != (const void *)d_keys) {
+        const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
         SP_HIP(ctx, hipMemcpyAsync(d_keys, keys, (size_t)n * 8, kind, ctx->stream));
         SP_HIP(ctx, hipMemcpyAsync(d_sg, sg, (size_t)n, kind, ctx->stream));
     }
-    if (compact) {
-        const int64_t nb = (int64_t)1 << bb;
-        int64_t ovf_n = 4096;
-        while (ovf_n < n / 2) ovf_n <<= 1;
-        rcb = sp_buf_ensure(ctx, ctx->b_ctab, nb * 16);
-        if (rcb) return rcb;
-        rcb = sp_buf_ensure(ctx, ctx->b_covf, ovf_n * 8);
-        if (rcb) return rcb;
-        SP_HIP(ctx, hipMemsetAsync(ctx->b_ctab.p, 0, (size_t)nb * 16, ctx->stream));
-        SP_HIP(ctx, hipMemsetAsync(ctx->b_covf.p, 0, (size_t)ovf_n * 8, ctx->stream));
-        ctx->ct_bb = bb;
-        ctx->ct_ovf_mask = (uint32_t)(ovf_n - 1);
-        if (n > 0)
-            SP_LAUNCH(ctx, "k4_ctab_build", k4_ctab_build, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                      (const unsigned long long *)d_keys, (const uint8_t *)d_sg, n, ctx->k, map_ptab_of(ctx), d_flags + 2);
-    }
-    auto build_direct = [&]() -> int {
-        int rc2 = sp_buf_ensure(ctx, ctx->b_ptab, entries * 4);
-        if (rc2) return rc2;
-        if (!table_clean) SP_HIP(ctx, hipMemsetAsync(ctx->b_ptab.p, 0, (size_t)entries * 4, ctx->stream));
-        if (n > 0)
-            SP_LAUNCH(ctx, "k4_pair_table", k4_pair_table, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                      (const unsigned long long *)d_keys, (const uint8_t *)d_sg, n, ctx->k, (uint32_t *)ctx->b_ptab.p);
-        ctx->ptab_k = ctx->k;
-        ctx->ptab_n = n;
-        return SP_OK;
-    };
-    if (ctx->map_engine == 0 && !compact) {
-        rcb = build_direct();
-        if (rcb) return rcb;
-    } else if (ctx->map_engine != 0) {
-        if (!ctx->d_label) SP_HIP(ctx, hipMalloc(&ctx->d_label, (size_t)ctx->nslots));
-        SP_HIP(ctx, hipMemsetAsync(ctx->d_label, 0, (size_t)ctx->nslots, ctx->stream));
-        if (n > 0) {
-            const sp_kparams kp = sp_make_kparams(ctx->k);
-            SP_LAUNCH(ctx, "k4_labels", k4_labels, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                      (const unsigned long long *)d_keys, (const uint8_t *)d_sg, n, kp, ctx->d_label);
-        }
-    }
-    const int rcf = sp_map_filter_build(ctx, n > 0 ? d_keys : nullptr, n);
-    if (rcf) return rcf;
-    SP_LAUNCH(ctx, "k4_flags_out", k4_flags_out, dim3(1), dim3(64), 0, (const unsigned long long *)d_flags, ctx->h_lflags);
-    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    int rcl = label_check();
-    if (rcl) return rcl;
-    if (compact && n > 0) {
-        const unsigned long long hf[2] = {ctx->h_lflags[2], ctx->h_lflags[3]};
-        if (getenv("SP_DEBUG_FILTER"))
+    if ((rc = labels_build(ctx, plan, d_keys, d_sg, n, table_clean, d_flags))) return rc;
+    if ((rc = sp_map_filter_build(ctx, n > 0 ? d_keys : nullptr, n))) return rc;
+    if ((rc = flags_out())) return rc;
+    if (plan.bb && n > 0) {
+        if (getenv("SP_DEBUG_FILTER") && plan.kind == SP_LABELS_COMPACT)
             fprintf(stderr, "[sp] compact pair table: 2^%d buckets, %llu entries in the overflow table (%lld labelled k-mers)\n",
-                    bb, hf[1], (long long)n);
-        if (hf[0]) {          // overflow table full (adversarial key sets only): the direct table takes over
-            ctx->ct_bb = 0;
-            table_clean = false;
-            rcb = build_direct();
-            if (rcb) return rcb;
+                    plan.bb, ctx->h_lflags[3], (long long)n);
+        if (getenv("SP_DEBUG_FILTER") && plan.kind == SP_LABELS_QUAD)
+            fprintf(stderr, "[sp] quad-bucket table (k > 15): 2^%d buckets, %llu entries in the overflow table (%lld labelled k-mers)\n",
+                    plan.bb, ctx->h_lflags[3], (long long)n);
+        if (ctx->h_lflags[2]) {          // overflow table full (adversarial key sets only): the plain table takes over
+            plan = sp_label_plan_fallback(plan, n);
+            if ((rc = labels_build(ctx, plan, d_keys, d_sg, n, false, d_flags))) return rc;
             SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
         }
     }
-    ctx->labels_ready = true;
+    ctx->labels.ready = true;
     return SP_OK;
 }
 
@@ -1142,8 +1222,7 @@ int sp_map_bins(sp_ctx *ctx, int chrom, int64_t bin_size, int64_t chunk_size, in
     if (!ctx || !slot_counts || chrom < 0 || chrom >= (int)ctx->chroms.size() || bin_size < 1 ||
         chunk_size < 0)
         return sp_fail(ctx, SP_EINVAL, "sp_map_bins: bad arguments");
-    if (!(ctx->sparse_mode ? ctx->d_hkeys != nullptr : ctx->labels_ready))
-        return sp_fail(ctx, SP_EINVAL, "sp_map_bins: call sp_labels_set first");
+    if (map_need_labels(ctx, "sp_map_bins")) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     sp_chrom &c = ctx->chroms[(size_t)chrom];
     const int S = ctx->n_sg;
@@ -1157,31 +1236,12 @@ int sp_map_bins(sp_ctx *ctx, int chrom, int64_t bin_size, int64_t chunk_size, in
     int *d_counts = (int *)ctx->b_map.p;
     unsigned long long *d_n = (unsigned long long *)((char *)d_counts + bytes8);
     SP_HIP(ctx, hipMemsetAsync(d_counts, 0, bytes8 + 8, ctx->stream));
-    sp_map_params P;
-    P.n_units = (c.len + SP_UNIT - 1) / SP_UNIT;
-    P.bin_size = bin_size;
-    P.chunk_size = chunk_size;
-    P.nslots = nslots;
-    P.S = S;
-    int64_t local = MAP_RANGE / bin_size + 3 + (chunk_size > 0 ? MAP_RANGE / chunk_size + 2 : 0);
-    P.use_lds = (local * S <= MAP_LDS_ENTRIES) ? 1 : 0;
-    if (ctx->sparse_mode) {
-        int rcs = sp_sparse_map_launch(ctx, c, P, d_counts, d_n);
-        if (rcs) return rcs;
-    } else if (P.n_units > 0) {
-        const sp_kparams32 kp = sp_make_kparams32(ctx->k);
-        int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-        int64_t grid = n_ranges;
-        if (grid > (int64_t)ctx->n_cu * MAP_GRID_MULT) grid = (int64_t)ctx->n_cu * MAP_GRID_MULT;
-        if (ctx->map_engine == 0) {
-            std::vector<map_chrom_desc> hd(1);
-            hd[0] = map_chrom_desc{c.d_pk, c.d_pm, c.d_nm, P.n_units, nslots, 0, d_counts, d_n};
-            int rcl = map_launch_dense(ctx, hd, n_ranges, P);
-            if (rcl) return rcl;
-        } else
-            SP_LAUNCH(ctx, "k5_map_lab", k5_map_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
-                      ctx->d_label, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
-    }
+    const sp_map_params P = map_params_of(c.len, bin_size, chunk_size, nslots, S);
+    std::vector<map_chrom_desc> hd;
+    int64_t hd_ranges = 0;
+    int rcl = map_bins_launch(ctx, c, P, d_counts, d_n, hd, hd_ranges);
+    if (!rcl) rcl = map_bins_flush(ctx, hd, hd_ranges, P);
+    if (rcl) return rcl;
     unsigned long long hn = 0;
     SP_HIP(ctx, hipMemcpyAsync(slot_counts, d_counts, bytes, hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP(ctx, hipMemcpyAsync(&hn, d_n, 8, hipMemcpyDeviceToHost, ctx->stream));
@@ -1194,8 +1254,7 @@ int sp_map_bins_all(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, const int
                     int32_t *slot_counts, int64_t *n_mapped) {
     if (!ctx || !slot_off || !slot_counts || bin_size < 1 || chunk_size < 0)
         return sp_fail(ctx, SP_EINVAL, "sp_map_bins_all: bad arguments");
-    if (!(ctx->sparse_mode ? ctx->d_hkeys != nullptr : ctx->labels_ready))
-        return sp_fail(ctx, SP_EINVAL, "sp_map_bins_all: call sp_labels_set first");
+    if (map_need_labels(ctx, "sp_map_bins_all")) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const int C = (int)ctx->chroms.size();
     const int S = ctx->n_sg;
@@ -1212,48 +1271,15 @@ int sp_map_bins_all(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, const int
     int *d_counts = (int *)ctx->b_map.p;
     unsigned long long *d_n = (unsigned long long *)((char *)d_counts + bytes8);
     SP_HIP(ctx, hipMemsetAsync(d_counts, 0, bytes8 + 8 * (size_t)C, ctx->stream));
-    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
-    int64_t local = MAP_RANGE / bin_size + 3 + (chunk_size > 0 ? MAP_RANGE / chunk_size + 2 : 0);
-    std::vector<map_chrom_desc> hd;     // pair-table engine: every chromosome in ONE launch
-    int64_t all_ranges = 0;
-    sp_map_params Pall;
-    Pall.n_units = 0;
-    Pall.bin_size = bin_size;
-    Pall.chunk_size = chunk_size;
-    Pall.nslots = 0;
-    Pall.S = S;
-    Pall.use_lds = (local * S <= MAP_LDS_ENTRIES) ? 1 : 0;
+    std::vector<map_chrom_desc> hd;     // pair-table kinds: every chromosome in ONE launch
+    int64_t hd_ranges = 0;
     for (int i = 0; i < C; i++) {
-        sp_chrom &c = ctx->chroms[(size_t)i];
-        sp_map_params P;
-        P.n_units = (c.len + SP_UNIT - 1) / SP_UNIT;
-        P.bin_size = bin_size;
-        P.chunk_size = chunk_size;
-        P.nslots = slot_off[i + 1] - slot_off[i];
-        P.S = S;
-        P.use_lds = (local * S <= MAP_LDS_ENTRIES) ? 1 : 0;
-        if (P.n_units == 0) continue;
-        if (ctx->sparse_mode) {
-            int rcs = sp_sparse_map_launch(ctx, c, P, d_counts + slot_off[i] * S, d_n + i);
-            if (rcs) return rcs;
-            continue;
-        }
-        int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-        if (ctx->map_engine == 0) {
-            hd.push_back(map_chrom_desc{c.d_pk, c.d_pm, c.d_nm, P.n_units, P.nslots, all_ranges, d_counts + slot_off[i] * S,
-                                        d_n + i});
-            all_ranges += n_ranges;
-            continue;
-        }
-        int64_t grid = n_ranges;
-        if (grid > (int64_t)ctx->n_cu * MAP_GRID_MULT) grid = (int64_t)ctx->n_cu * MAP_GRID_MULT;
-        SP_LAUNCH(ctx, "k5_map_lab", k5_map_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
-                  ctx->d_label, ctx->d_bloom, ctx->bloom_bits, d_counts + slot_off[i] * S, d_n + i);
-    }
-    if (!hd.empty()) {
-        int rcl = map_launch_dense(ctx, hd, all_ranges, Pall);
+        const sp_map_params P = map_params_of(ctx->chroms[(size_t)i].len, bin_size, chunk_size, slot_off[i + 1] - slot_off[i], S);
+        int rcl = map_bins_launch(ctx, ctx->chroms[(size_t)i], P, d_counts + slot_off[i] * S, d_n + i, hd, hd_ranges);
         if (rcl) return rcl;
     }
+    int rcl = map_bins_flush(ctx, hd, hd_ranges, map_params_of(0, bin_size, chunk_size, 0, S));
+    if (rcl) return rcl;
     SP_HIP(ctx, hipMemcpyAsync(slot_counts, d_counts, bytes, hipMemcpyDeviceToHost, ctx->stream));
     std::vector<unsigned long long> hn((size_t)C, 0);
     SP_HIP(ctx, hipMemcpyAsync(hn.data(), d_n, 8 * (size_t)C, hipMemcpyDeviceToHost, ctx->stream));
@@ -1350,8 +1376,7 @@ int sp_map_features(sp_ctx *ctx, const uint8_t *ascii, const int64_t *off, int64
                     int64_t *counts) {
     if (!ctx || !off || !counts || n_feat < 0 || (n_feat > 0 && off[n_feat] > 0 && !ascii))
         return sp_fail(ctx, SP_EINVAL, "sp_map_features: bad arguments");
-    if (!(ctx->sparse_mode ? ctx->d_hkeys != nullptr : ctx->labels_ready))
-        return sp_fail(ctx, SP_EINVAL, "sp_map_features: call sp_labels_set first");
+    if (map_need_labels(ctx, "sp_map_features")) return SP_EINVAL;
     const int S = ctx->n_sg;
     memset(counts, 0, (size_t)n_feat * S * sizeof(int64_t));
     if (n_feat == 0) return SP_OK;
@@ -1383,28 +1408,8 @@ int sp_map_features(sp_ctx *ctx, const uint8_t *ascii, const int64_t *off, int64
     SP_LAUNCH(ctx, "k0_pack", k0_pack, dim3((unsigned)blocks), dim3(256), 0, (const uint8_t *)d_ascii.p, total, d_pk.p,
               d_pk.p + 2 * nmw, d_nm.p, nmw);
     int64_t n_units = (total + SP_UNIT - 1) / SP_UNIT;
-    if (ctx->sparse_mode) {
-        int rcs = sp_sparse_feat_launch(ctx, d_pk.p, d_pk.p + 2 * nmw, d_nm.p, n_units, d_foff.p, n_feat, S, d_counts.p);
-        if (rcs) return rcs;
-    } else {
-        const sp_kparams32 kp = sp_make_kparams32(ctx->k);
-        int64_t grid = (n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-        if (grid > (int64_t)ctx->n_cu * MAP_GRID_MULT) grid = (int64_t)ctx->n_cu * MAP_GRID_MULT;
-        if (ctx->map_engine == 0 && ctx->ct_bb)
-            SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const uint32_t *)d_pk.p,
-                      (const uint32_t *)(d_pk.p + 2 * nmw), (const uint32_t *)d_nm.p, kp, n_units,
-                      (const int64_t *)d_foff.p, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom,
-                      ctx->bloom_bits, d_counts.p);
-        else if (ctx->map_engine == 0)
-            SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const uint32_t *)d_pk.p,
-                      (const uint32_t *)(d_pk.p + 2 * nmw), (const uint32_t *)d_nm.p, kp, n_units,
-                      (const int64_t *)d_foff.p, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom,
-                      ctx->bloom_bits, d_counts.p);
-        else
-            SP_LAUNCH(ctx, "k5_map_feat_lab", k5_map_feat_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0,
-                      (const uint32_t *)d_pk.p, (const uint32_t *)d_nm.p, kp, n_units, (const int64_t *)d_foff.p, n_feat,
-                      S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts.p);
-    }
+    int rcl = map_feat_launch(ctx, d_pk.p, d_pk.p + 2 * nmw, d_nm.p, n_units, d_foff.p, n_feat, S, d_counts.p);
+    if (rcl) return rcl;
     SP_HIP(ctx, hipMemcpyAsync(counts, d_counts, (size_t)n_feat * S * 8, hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     return SP_OK;
@@ -1414,8 +1419,7 @@ int sp_map_intervals(sp_ctx *ctx, const int32_t *chrom, const int64_t *start, co
                      int64_t *counts) {
     if (!ctx || n < 0 || (n > 0 && (!chrom || !start || !end || !counts)))
         return sp_fail(ctx, SP_EINVAL, "sp_map_intervals: bad arguments");
-    if (!(ctx->sparse_mode ? ctx->d_hkeys != nullptr : ctx->labels_ready))
-        return sp_fail(ctx, SP_EINVAL, "sp_map_intervals: call sp_labels_set first");
+    if (map_need_labels(ctx, "sp_map_intervals")) return SP_EINVAL;
     const int C = (int)ctx->chroms.size(), S = ctx->n_sg, k = ctx->k;
     for (int64_t i = 0; i < n; i++) {
         if (chrom[i] < 0 || chrom[i] >= C) return sp_fail(ctx, SP_EINVAL, "sp_map_intervals: interval %lld: chromosome %d out of range", (long long)i, chrom[i]);
@@ -1452,26 +1456,8 @@ int sp_map_intervals(sp_ctx *ctx, const int32_t *chrom, const int64_t *start, co
         sp_chrom &ch = ctx->chroms[(size_t)c];
         const int64_t n_units = (ch.len + SP_UNIT - 1) / SP_UNIT;
         if (n_units == 0) continue;
-        if (ctx->sparse_mode) {
-            int rcs = sp_sparse_mask_launch(ctx, ch, n_units, S, d_cov + ubase[(size_t)c], d_masks + ubase[(size_t)c] * S);
-            if (rcs) return rcs;
-            continue;
-        }
-        const sp_kparams32 kp = sp_make_kparams32(k);
-        int64_t grid = (n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-        if (grid > (int64_t)ctx->n_cu * MAP_GRID_MULT) grid = (int64_t)ctx->n_cu * MAP_GRID_MULT;
-        if (ctx->map_engine == 0 && ctx->ct_bb)
-            SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, ch.d_pk, ch.d_pm, ch.d_nm, kp,
-                      n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits,
-                      (const unsigned long long *)(d_cov + ubase[(size_t)c]), d_masks + ubase[(size_t)c] * S);
-        else if (ctx->map_engine == 0)
-            SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, ch.d_pk, ch.d_pm, ch.d_nm, kp,
-                      n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits,
-                      (const unsigned long long *)(d_cov + ubase[(size_t)c]), d_masks + ubase[(size_t)c] * S);
-        else
-            SP_LAUNCH(ctx, "k5_map_mask_lab", k5_map_mask_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, ch.d_pk, ch.d_nm,
-                      kp, n_units, S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits,
-                      (const unsigned long long *)(d_cov + ubase[(size_t)c]), d_masks + ubase[(size_t)c] * S);
+        int rcl = map_mask_launch(ctx, ch, n_units, S, d_cov + ubase[(size_t)c], d_masks + ubase[(size_t)c] * S);
+        if (rcl) return rcl;
     }
     SP_LAUNCH(ctx, "kv_count", kv_count, dim3((unsigned)gw), dim3(256), 0, (const int32_t *)d_ch, (const int64_t *)d_st,
               (const int64_t *)d_en, n, k, S, (const int64_t *)d_ub, (const unsigned long long *)d_masks, d_counts);
@@ -1482,30 +1468,14 @@ int sp_map_intervals(sp_ctx *ctx, const int32_t *chrom, const int64_t *start, co
 
 int sp_labels_hit(sp_ctx *ctx, int64_t *n_hit) {
     if (!ctx || !n_hit) return sp_fail(ctx, SP_EINVAL, "sp_labels_hit: bad arguments");
-    if (!(ctx->sparse_mode ? ctx->d_hkeys != nullptr : ctx->labels_ready))
-        return sp_fail(ctx, SP_EINVAL, "sp_labels_hit: call sp_labels_set first");
+    if (map_need_labels(ctx, "sp_labels_hit")) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     sp_tmp<unsigned long long> d_n;
     unsigned long long h = 0;
     SP_HIP(ctx, d_n.alloc(1));
     SP_HIP(ctx, hipMemsetAsync(d_n.p, 0, 8, ctx->stream));
-    if (ctx->sparse_mode) {
-        int rcs = sp_sparse_hit(ctx, d_n.p);
-        if (rcs) return rcs;
-    } else {
-        if (ctx->map_engine == 0) {
-            if (ctx->n_labels > 0 && ctx->ct_bb)
-                SP_LAUNCH(ctx, "k4_ctab_seen", k4_ctab_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
-                          (const unsigned long long *)ctx->b_labkeys.p, ctx->n_labels, ctx->k, map_ptab_of(ctx), d_n.p);
-            else if (ctx->n_labels > 0)
-                SP_LAUNCH(ctx, "k4_pair_seen", k4_pair_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
-                          (const unsigned long long *)ctx->b_labkeys.p, ctx->n_labels, ctx->k,
-                          (const uint32_t *)ctx->b_ptab.p, d_n.p);
-        } else {
-            SP_LAUNCH(ctx, "k4_count_seen", k4_count_seen, dim3((unsigned)(ctx->n_cu * 8)), dim3(256), 0,
-                      (const uint8_t *)ctx->d_label, ctx->nslots, d_n.p);
-        }
-    }
+    int rcl = map_hit_launch(ctx, d_n.p);
+    if (rcl) return rcl;
     SP_HIP(ctx, hipMemcpyAsync(&h, d_n.p, 8, hipMemcpyDeviceToHost, ctx->stream));
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     *n_hit = (int64_t)h;

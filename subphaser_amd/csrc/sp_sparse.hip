@@ -201,7 +201,7 @@ sps_pair_seen(const unsigned long long *__restrict__ keys, int64_t n, int k, con
     if (threadIdx.x == 0 && t) atomicAdd(out, t);
 }
 
-// K5 for k > 15, per-k-mer table (more than 7 subgenomes, or SP_MAP_ENGINE=1): the rolling scan, one filter probe per pair
+// K5 for k > 15, per-k-mer table (SP_LABELS_KMER_HASH: more than 7 subgenomes, or on demand -- sp_labelplan.h): the rolling scan, one filter probe per pair
 // of starts, one 16-byte look-up per candidate start.  (The pair-keyed table takes k5_map_sparse2 below; the unrolled
 // pair kernel of rounds 1-4 -- 532 KB of machine code -- was removed in round 6.)
 __global__ void __launch_bounds__(MAP_BLOCK)
@@ -263,7 +263,7 @@ k5_map_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ 
 #define SQ_ANY 0x6DB6DBULL
 #define SQ_PAYLOAD 0xFFFFFFULL
 #define SQ_OVF (1ULL << 24)
-#define SQ_TAG_BITS 39
+// (SQ_TAG_BITS = 39: sp_labelplan.h, the sizing needs it)
 struct sq_tab {
     unsigned long long *buckets;      // 4 entries (32 bytes) per bucket, or NULL: the pair-keyed hash table is in use
     unsigned long long *ovf;          // overflow table: {key id + 1, fields} pairs, 0 = empty
@@ -930,163 +930,104 @@ int sp_sparse_dump(sp_ctx *ctx, int chrom, uint64_t *keys, uint32_t *counts) {
 
 // the quad-bucket table the current k > 15 label set lives in (buckets = NULL: the pair-keyed / per-k-mer hash table)
 static sq_tab sq_tab_of(const sp_ctx *ctx) {
+    const bool quad = ctx->labels.kind == SP_LABELS_QUAD;
     sq_tab T;
-    T.buckets = ctx->sq_bb ? (unsigned long long *)ctx->b_ctab.p : nullptr;
+    T.buckets = quad ? (unsigned long long *)ctx->b_ctab.p : nullptr;
     T.ovf = (unsigned long long *)ctx->b_covf.p;
-    T.ovf_mask = ctx->sq_ovf_mask;
+    T.ovf_mask = ctx->labels.ovf_mask;
     T.sb = 2 * (ctx->k - 3);
-    T.tb = ctx->sq_bb ? T.sb - ctx->sq_bb : 0;
+    T.tb = quad ? T.sb - ctx->labels.bb : 0;
     return T;
 }
 
-int sp_sparse_labels_set(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg, int64_t n, bool on_device) {
-    // <= 7 subgenomes: the pair-keyed table (one look-up per candidate PAIR of starts); else one entry per k-mer
-    const char *eng = getenv("SP_MAP_ENGINE");
-    ctx->map_engine = (ctx->n_sg > 7 || (eng && eng[0] == '1')) ? 1 : 0;
-    const bool pairs = ctx->map_engine == 0;
-    // round 6: <= 3 subgenomes -> the quad-bucket table (one 32-byte look-up per candidate QUAD of starts) when its tag fits;
-    // SP_CTAB=0 keeps the pair-keyed hash table (cross-check), SP_CTAB_FACTOR sizes the buckets (default: >= 2 n of them)
-    ctx->sq_bb = 0;
-    int bb = 8;
-    bool quad = false;
-    if (pairs && ctx->n_sg <= 3) {
-        const char *env_ct = getenv("SP_CTAB"), *env_f = getenv("SP_CTAB_FACTOR");
-        const int64_t factor = env_f && atoll(env_f) > 0 ? atoll(env_f) : 2;
-        const int sb = 2 * (ctx->k - 3);
-        while (bb < 30 && ((int64_t)1 << bb) < factor * (n > 0 ? n : 1)) bb++;
-        if (bb < sb - (SQ_TAG_BITS - 5)) bb = sb - (SQ_TAG_BITS - 5);      // the tag holds sb - bb bits of the mixed core + side + e
-        quad = bb <= 27 && bb <= sb && !(env_ct && env_ct[0] == '0');
-    }
-    int64_t cap = 1024;
-    if (!quad)
-        while (cap < (pairs ? 4 : 2) * n + 16) cap <<= 1;
-    if (cap != ctx->hcap) {
-        if (ctx->d_hkeys) hipFree(ctx->d_hkeys);
-        ctx->d_hkeys = nullptr;
-        SP_HIP(ctx, hipMalloc(&ctx->d_hkeys, (size_t)cap * 16));
-        ctx->hcap = cap;
-    }
-    if (quad) {
-        // (d_hkeys stays allocated -- it is what "labels are set" is tested by -- but unused)
-        const int64_t nb = (int64_t)1 << bb;
-        int64_t ovf_n = 4096;
-        while (ovf_n < n / 2) ovf_n <<= 1;
-        int rcq = sp_buf_ensure(ctx, ctx->b_ctab, nb * 32);
-        if (rcq) return rcq;
-        rcq = sp_buf_ensure(ctx, ctx->b_covf, ovf_n * 16);
-        if (rcq) return rcq;
-        SP_HIP(ctx, hipMemsetAsync(ctx->b_ctab.p, 0, (size_t)nb * 32, ctx->stream));
-        SP_HIP(ctx, hipMemsetAsync(ctx->b_covf.p, 0, (size_t)ovf_n * 16, ctx->stream));
-        ctx->sq_bb = bb;
-        ctx->sq_ovf_mask = (uint64_t)(ovf_n - 1);
-    } else if (pairs) {
-        SP_LAUNCH(ctx, "sps_pair_init", sps_pair_init, dim3((unsigned)(ctx->n_cu * 8)), dim3(256), 0,
-                  (unsigned long long *)ctx->d_hkeys, cap);
-    } else {
-        // {key = sentinel (all ones), label = 0}: 0xff everywhere, then the label words are written on insert
-        // and read only after a key match, so they need no clearing
-        SP_HIP(ctx, hipMemsetAsync(ctx->d_hkeys, 0xff, (size_t)cap * 16, ctx->stream));
-    }
-    if (n == 0) return sp_map_filter_build(ctx, nullptr, 0);
-    // the labelled keys stay on the device (sp_labels_hit walks them in pair mode); the dense engine's pair table, if
-    // any, was built from the keys this overwrites: it must be cleared in full next time
-    ctx->ptab_k = 0;
-    ctx->ptab_n = 0;
-    int rcb = sp_buf_ensure(ctx, ctx->b_labkeys, n * 9 + 64);
-    if (rcb) return rcb;
-    unsigned long long *d_keys = (unsigned long long *)ctx->b_labkeys.p;
-    uint8_t *d_sg = (uint8_t *)(d_keys + n);
-    const hipMemcpyKind kind = on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    SP_HIP(ctx, hipMemcpyAsync(d_keys, keys, (size_t)n * 8, kind, ctx->stream));
-    SP_HIP(ctx, hipMemcpyAsync(d_sg, sg, (size_t)n, kind, ctx->stream));
-    auto build_pairs = [&]() -> int {
-        SP_LAUNCH(ctx, "sps_pair_insert", sps_pair_insert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                  (const unsigned long long *)d_keys, (const uint8_t *)d_sg, n, ctx->k, (unsigned long long *)ctx->d_hkeys,
-                  (uint64_t)(ctx->hcap - 1));
-        return SP_OK;
-    };
-    if (quad) {
-        // [2] = overflow table full, [3] = keys in the overflow table (the flags of this call: sp_labels_set zeroed them)
-        unsigned long long *d_flags = (unsigned long long *)ctx->b_lflags.p;
-        SP_LAUNCH(ctx, "sq_build", sq_build, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (const unsigned long long *)d_keys,
-                  (const uint8_t *)d_sg, n, ctx->k, sq_tab_of(ctx), d_flags + 2);
-        unsigned long long hf[2] = {0, 0};
-        SP_HIP(ctx, hipMemcpyAsync(hf, d_flags + 2, 16, hipMemcpyDeviceToHost, ctx->stream));
-        SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-        if (getenv("SP_DEBUG_FILTER"))
-            fprintf(stderr, "[sp] quad-bucket table (k > 15): 2^%d buckets, %llu entries in the overflow table (%lld labelled k-mers)\n",
-                    bb, hf[1], (long long)n);
-        if (hf[0]) {          // overflow table full (adversarial key sets only): the pair-keyed hash table takes over
-            ctx->sq_bb = 0;
-            cap = 1024;
-            while (cap < 4 * n + 16) cap <<= 1;
-            if (cap != ctx->hcap) {
-                if (ctx->d_hkeys) hipFree(ctx->d_hkeys);
-                ctx->d_hkeys = nullptr;
-                SP_HIP(ctx, hipMalloc(&ctx->d_hkeys, (size_t)cap * 16));
-                ctx->hcap = cap;
-            }
-            SP_LAUNCH(ctx, "sps_pair_init", sps_pair_init, dim3((unsigned)(ctx->n_cu * 8)), dim3(256), 0,
-                      (unsigned long long *)ctx->d_hkeys, cap);
-            const int rcp = build_pairs();
-            if (rcp) return rcp;
-        }
-    } else if (pairs) {
-        const int rcp = build_pairs();
-        if (rcp) return rcp;
-    } else
-        SP_LAUNCH(ctx, "sps_hash_insert", sps_hash_insert, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
-                  (const unsigned long long *)d_keys, (const uint8_t *)d_sg, n, (unsigned long long *)ctx->d_hkeys,
-                  (uint64_t)(ctx->hcap - 1));
-    const int rcf = sp_map_filter_build(ctx, d_keys, n);
-    SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    return rcf;
+// the hash table of the k > 15 kinds: `cap` 16-byte entries (1024 unused ones beside the quad-bucket table: every map
+// kernel takes the pointer)
+static int sps_hash_ensure(sp_ctx *ctx, int64_t cap) {
+    if (cap == ctx->hcap) return SP_OK;
+    if (ctx->d_hkeys) hipFree(ctx->d_hkeys);
+    ctx->d_hkeys = nullptr;
+    ctx->hcap = 0;
+    SP_HIP(ctx, hipMalloc(&ctx->d_hkeys, (size_t)cap * 16));
+    ctx->hcap = cap;
+    return SP_OK;
 }
 
+// sp_labels_set at k > 15 (the driver: sp_map.hip): the planned table, already the context's label state, from the staged keys
+int sp_sparse_labels_build(sp_ctx *ctx, const sp_label_plan &plan, const unsigned long long *d_keys, const uint8_t *d_sg,
+                           int64_t n, unsigned long long *d_flags) {
+    const unsigned grid = (unsigned)((n + 255) / 256);
+    int rc = sps_hash_ensure(ctx, plan.cap);
+    if (rc) return rc;
+    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
+    switch (plan.kind) {
+    case SP_LABELS_QUAD:
+        if ((rc = sp_buf_ensure(ctx, ctx->b_ctab, plan.bucket_bytes))) return rc;
+        if ((rc = sp_buf_ensure(ctx, ctx->b_covf, plan.ovf_bytes))) return rc;
+        SP_HIP(ctx, hipMemsetAsync(ctx->b_ctab.p, 0, (size_t)plan.bucket_bytes, ctx->stream));
+        SP_HIP(ctx, hipMemsetAsync(ctx->b_covf.p, 0, (size_t)plan.ovf_bytes, ctx->stream));
+        if (n > 0)      // d_flags[2] = overflow table full, [3] = keys in the overflow table
+            SP_LAUNCH(ctx, "sq_build", sq_build, dim3(grid), dim3(256), 0, d_keys, d_sg, n, ctx->k, sq_tab_of(ctx), d_flags + 2);
+        return SP_OK;
+    case SP_LABELS_PAIR_HASH:
+        SP_LAUNCH(ctx, "sps_pair_init", sps_pair_init, dim3((unsigned)(ctx->n_cu * 8)), dim3(256), 0, htab, plan.cap);
+        if (n > 0)
+            SP_LAUNCH(ctx, "sps_pair_insert", sps_pair_insert, dim3(grid), dim3(256), 0, d_keys, d_sg, n, ctx->k, htab,
+                      (uint64_t)(plan.cap - 1));
+        return SP_OK;
+    default:      // SP_LABELS_KMER_HASH
+        // {key = sentinel (all ones), label = 0}: 0xff everywhere, then the label words are written on insert
+        // and read only after a key match, so they need no clearing
+        SP_HIP(ctx, hipMemsetAsync(htab, 0xff, (size_t)plan.cap * 16, ctx->stream));
+        if (n > 0)
+            SP_LAUNCH(ctx, "sps_hash_insert", sps_hash_insert, dim3(grid), dim3(256), 0, d_keys, d_sg, n, htab,
+                      (uint64_t)(plan.cap - 1));
+        return SP_OK;
+    }
+}
+
+// The k > 15 half of the four dispatches of sp_map.hip: SP_LABELS_QUAD, SP_LABELS_PAIR_HASH, else SP_LABELS_KMER_HASH
 int sp_sparse_map_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n) {
     if (P.n_units == 0) return SP_OK;
     const sp_kparams kp = sp_make_kparams(ctx->k);
-    int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    int64_t grid = n_ranges;
-    if (grid > (int64_t)ctx->n_cu * 16) grid = (int64_t)ctx->n_cu * 16;
-    if (ctx->map_engine == 0 && P.S <= 7) {
-        const sq_tab T = sq_tab_of(ctx);
-        if (T.buckets)
-            SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
-                      (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), T, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
-        else
-            SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
-                      (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), T, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+    const int64_t grid = map_grid(ctx, (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK);
+    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
+    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_QUAD:
+        SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
+                  htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+        return SP_OK;
+    case SP_LABELS_PAIR_HASH:
+        SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
+                  htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+        return SP_OK;
+    default:
+        SP_LAUNCH(ctx, "k5_map_sparse_lab", k5_map_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
+                  htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
         return SP_OK;
     }
-    if (ctx->map_engine == 0) return sp_fail(ctx, SP_ESTATE, "k > 15 map: the pair-keyed table holds at most 7 subgenomes");
-    SP_LAUNCH(ctx, "k5_map_sparse_lab", k5_map_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
-              (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
-    return SP_OK;
 }
 
 int sp_sparse_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
                           const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts) {
     const sp_kparams kp = sp_make_kparams(ctx->k);
-    int64_t grid = (n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    if (grid > (int64_t)ctx->n_cu * 16) grid = (int64_t)ctx->n_cu * 16;
-    if (ctx->map_engine == 0 && S <= 7) {
-        const sq_tab T = sq_tab_of(ctx);
-        if (T.buckets)
-            SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
-                      kp, n_units, d_foff, n_feat, S, (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), T, ctx->d_bloom,
-                      ctx->bloom_bits, d_counts);
-        else
-            SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
-                      kp, n_units, d_foff, n_feat, S, (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), T, ctx->d_bloom,
-                      ctx->bloom_bits, d_counts);
-    } else if (ctx->map_engine == 0)
-        return sp_fail(ctx, SP_ESTATE, "k > 15 map: the pair-keyed table holds at most 7 subgenomes");
-    else
+    const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
+    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
+    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_QUAD:
+        SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
+                  kp, n_units, d_foff, n_feat, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    case SP_LABELS_PAIR_HASH:
+        SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
+                  kp, n_units, d_foff, n_feat, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    default:
         SP_LAUNCH(ctx, "k5_map_feat_sparse_lab", k5_map_feat_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp,
-                  n_units, d_foff, n_feat, S, (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), ctx->d_bloom,
-                  ctx->bloom_bits, d_counts);
-    return SP_OK;
+                  n_units, d_foff, n_feat, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts);
+        return SP_OK;
+    }
 }
 
 // interval mode (sp_map.hip: kv_cover / kv_count): the k > 15 scan that fills the per-unit subgenome masks
@@ -1131,44 +1072,43 @@ k5_map_mask_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict_
 int sp_sparse_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, const unsigned long long *d_cov,
                           unsigned long long *d_masks) {
     const sp_kparams kp = sp_make_kparams(ctx->k);
-    int64_t grid = (n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    if (grid > (int64_t)ctx->n_cu * 16) grid = (int64_t)ctx->n_cu * 16;
-    if (ctx->map_engine == 0 && S <= 7) {
-        const sq_tab T = sq_tab_of(ctx);
-        if (T.buckets)
-            SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const uint32_t *)c.d_pk,
-                      (const uint32_t *)c.d_pm, (const uint32_t *)c.d_nm, kp, n_units, S, (unsigned long long *)ctx->d_hkeys,
-                      (uint64_t)(ctx->hcap - 1), T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-        else
-            SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const uint32_t *)c.d_pk,
-                      (const uint32_t *)c.d_pm, (const uint32_t *)c.d_nm, kp, n_units, S, (unsigned long long *)ctx->d_hkeys,
-                      (uint64_t)(ctx->hcap - 1), T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+    const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
+    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
+    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_QUAD:
+        SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
+                  c.d_nm, kp, n_units, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        return SP_OK;
+    case SP_LABELS_PAIR_HASH:
+        SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
+                  c.d_nm, kp, n_units, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        return SP_OK;
+    default:
+        SP_LAUNCH(ctx, "k5_map_mask_sparse_lab", k5_map_mask_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
+                  kp, n_units, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
         return SP_OK;
     }
-    if (ctx->map_engine == 0) return sp_fail(ctx, SP_ESTATE, "k > 15 map: the pair-keyed table holds at most 7 subgenomes");
-    SP_LAUNCH(ctx, "k5_map_mask_sparse_lab", k5_map_mask_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const uint32_t *)c.d_pk,
-              (const uint32_t *)c.d_nm, kp, n_units, S, (unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1),
-              (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-    return SP_OK;
 }
 
 int sp_sparse_hit(sp_ctx *ctx, unsigned long long *d_n) {
-    if (ctx->map_engine == 0 && ctx->sq_bb) {
+    const unsigned long long *d_keys = (const unsigned long long *)ctx->b_labkeys.p;
+    switch (ctx->labels.kind) {
+    case SP_LABELS_QUAD:
         if (ctx->n_labels > 0)
-            SP_LAUNCH(ctx, "sq_seen", sq_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
-                      (const unsigned long long *)ctx->b_labkeys.p, ctx->n_labels, ctx->k, sq_tab_of(ctx), d_n);
+            SP_LAUNCH(ctx, "sq_seen", sq_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0, d_keys, ctx->n_labels, ctx->k,
+                      sq_tab_of(ctx), d_n);
+        return SP_OK;
+    case SP_LABELS_PAIR_HASH:
+        if (ctx->n_labels > 0)
+            SP_LAUNCH(ctx, "sps_pair_seen", sps_pair_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0, d_keys, ctx->n_labels,
+                      ctx->k, (const unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), d_n);
+        return SP_OK;
+    default:
+        SP_LAUNCH(ctx, "sps_count_seen", sps_count_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
+                  (const unsigned long long *)ctx->d_hkeys, ctx->hcap, d_n);
         return SP_OK;
     }
-    if (ctx->map_engine == 0) {
-        if (ctx->n_labels > 0)
-            SP_LAUNCH(ctx, "sps_pair_seen", sps_pair_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
-                      (const unsigned long long *)ctx->b_labkeys.p, ctx->n_labels, ctx->k,
-                      (const unsigned long long *)ctx->d_hkeys, (uint64_t)(ctx->hcap - 1), d_n);
-        return SP_OK;
-    }
-    SP_LAUNCH(ctx, "sps_count_seen", sps_count_seen, dim3((unsigned)(ctx->n_cu * 4)), dim3(256), 0,
-              (const unsigned long long *)ctx->d_hkeys, ctx->hcap, d_n);
-    return SP_OK;
 }
 
 // ------------------------------------------------------------------ multi-GPU support (k > 15)

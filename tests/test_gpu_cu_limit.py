@@ -40,19 +40,19 @@ work exceeded it.
     sps_join_wide (sp_listfilter.hip:1105)        16                   64 / 256 key ranges of 130 lists     >= 3 passes
     sps_bounds (sp_listfilter.hip:1199)           16 x 130 lists       576 / 2071 blocks a list             >= 3 passes
     row plan (sp_listplan.h, :1230/1270)          the slack of 16 x limit chunks is no grid: the rows are compared
-    k5_map (sp_map.hip:620)                       16                   47 / 104 ranges of 32 768 starts     >= 3 passes
-    k5_map_lab (sp_map.hip:1175/1249)             16                   21 / 51 ranges of chromosome 0       >= 2 passes
-    k5_map_sparse(_lab) (sp_sparse.hip:1051)      16                   21 / 51 ranges of chromosome 0       >= 2 passes
-    k5_map_feat(_lab) (sp_map.hip:1392)           16                   35 / 71 ranges of features           >= 2 passes
-    k5_map_feat_sparse(_lab) (sp_sparse.hip:1072) 16                   36 / 75 ranges of features           >= 2 passes
-    k5_map_mask(_lab) (sp_map.hip:1462)           16                   21 / 51 ranges of chromosome 0       >= 2 passes
-    k5_map_mask_sparse(_lab) (sp_sparse.hip:1135) 16                   21 / 51 ranges of chromosome 0       >= 2 passes
-    kv_cover, kv_count (sp_map.hip:1448)          32                   200 / 400 blocks of 4 intervals      >= 3 passes
-    k4_ctab_seen, k4_pair_seen (sp_map.hip:1498)  4                    7261 / 12 749 labels, 256 a block    >= 3 passes
-    k4_count_seen (sp_map.hip:1505)               8                    the label table of 2^29 slots        >= 3 passes
-    sq_seen, sps_pair_seen (sp_sparse.hip:1158)   4                    7154 / 12 255 labels, 256 a block    >= 3 passes
-    sps_count_seen (sp_sparse.hip:1169)           4                    the hash table's entries             >= 3 passes
-    sps_pair_init (sp_sparse.hip:983/1029)        8                    the hash table's entries             >= 3 passes
+    k5_map (sp_map.h map_grid, :980)              16                   47 / 104 ranges of 32 768 starts     >= 3 passes
+    k5_map_lab (map_grid, sp_map.hip:1004)        16                   21 / 51 ranges of chromosome 0       >= 2 passes
+    k5_map_sparse(_lab) (sp_sparse.hip:992)       16                   21 / 51 ranges of chromosome 0       >= 2 passes
+    k5_map_feat(_lab) (sp_map.hip:1016)           16                   35 / 71 ranges of features           >= 2 passes
+    k5_map_feat_sparse(_lab) (sp_sparse.hip:1014) 16                   36 / 75 ranges of features           >= 2 passes
+    k5_map_mask(_lab) (sp_map.hip:1039)           16                   21 / 51 ranges of chromosome 0       >= 2 passes
+    k5_map_mask_sparse(_lab) (sp_sparse.hip:1075) 16                   21 / 51 ranges of chromosome 0       >= 2 passes
+    kv_cover, kv_count (sp_map.hip:1452)          32                   200 / 400 blocks of 4 intervals      >= 3 passes
+    k4_ctab_seen, k4_pair_seen (sp_map.hip:1064)  4                    7261 / 12 749 labels, 256 a block    >= 3 passes
+    k4_count_seen (sp_map.hip:1073)               8                    the label table of 2^29 slots        >= 3 passes
+    sq_seen, sps_pair_seen (sp_sparse.hip:1099)   4                    7154 / 12 255 labels, 256 a block    >= 3 passes
+    sps_count_seen (sp_sparse.hip:1108)           4                    the hash table's entries             >= 3 passes
+    sps_pair_init (sp_sparse.hip:972)             8                    the hash table's entries             >= 3 passes
     bk_count, bk_build, bk_anchors (:293 bk_grid) 8                    18 / 52 blocks of 256 units          >= 2 passes
     bk_singles (sp_blocks.hip:293 bk_grid)        8                    214 / 621 blocks of index entries    >= 3 passes
     bk_pair (sp_blocks.hip:441)                   16                   141 / 421 windows                    >= 3 passes
@@ -64,7 +64,7 @@ factor being far away.)
 Not covered -- these never reach their cap here, or no stage of this file calls them:
     k3_slow (sp_filter.hip:878): the dense filter's slow queue stays empty on these genomes;
     kx_merge, kx_lengths (sp_count.hip:840/868): the multi-GPU table exchange (test_gpu_table_exchange.py);
-    k4_label_max (sp_map.hip:984): one workgroup below 65 536 labels;
+    k4_label_max (sp_map.hip:1152): one workgroup below 65 536 labels;
     c2_count (sp_count2.hip:1565): runs only under SP_C2_COUNT16=0;
     c2_count_list (sp_count2.hip:1579/1733): at most 256 buckets a workgroup, which sets its grid above the cap;
     s3_hist1_sample, s3_hist2, s3_final_small (the sites of s3_hist1, s3_hist2_sample and s3_final_bitmap under other

@@ -1001,7 +1001,7 @@ def test_map_vs_oracle_random(gpu_ctx, monkeypatch, k, S, flt):
 @pytest.mark.parametrize("k", [13, 15, 21])
 def test_labels_set_device(gpu_ctx, k):
     """sp_labels_set_device (the label set handed over in device memory, KmerLabels.on_device) maps exactly like
-    sp_labels_set; a label >= n_sg is caught on the device."""
+    sp_labels_set; a label >= n_sg is caught on the device, before anything of the previous label set is touched."""
     from subphaser_amd.seqs import KmerLabels
     rng = np.random.RandomState(77 + k)
     s = np.concatenate([_rand_seq(rng, 60_000), np.tile(_rand_seq(rng, 300, 0, 0), 30)])
@@ -1024,6 +1024,8 @@ def test_labels_set_device(gpu_ctx, k):
     d_keys, d_sg = lab.on_device(gpu_ctx)
     with pytest.raises(ValueError, match="label 2 >= n_sg 2"):
         gpu_ctx.labels_set_device(d_keys, d_sg, sel.size, 2)
+    again, n_again = gpu_ctx.map_bins(0, 777, 5000)      # the rejected hand-over left the previous label set usable
+    assert (again == got).all() and n_again == n
     lab.release_device()
 
 
