@@ -426,6 +426,27 @@ int sp_blocks_set_cells(sp_ctx *ctx, int cells);
 int sp_ltr_align(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *a_start, const int32_t *a_len,
                  const int64_t *b_start, const int32_t *b_len, int band, int32_t *out);
 
+/* ---- de novo LTR-RT detection on the resident genome --------------------------
+ * Exact seeds at a bounded distance and their gapless X-drop extensions on the forward strand of one chromosome; the
+ * definition -- word, partners (at most 32 successors looked at, 8 kept), left-maximal seeds, extension, the HSP word --
+ * is in csrc/sp_ltrdetect.h, the chaining of the HSPs into candidates in subphaser_amd/ltr.py.  Positions are 0-based.
+ *   sp_ltr_seeds   detects on chromosome `chrom` and keeps the HSP list of this call: the distinct (p0, len, d),
+ *                  ascending as tuples; *n_seeds = the seeds before extension, *n_hsps = the length of the list.  A
+ *                  chromosome shorter than seed_len has none.  No seed is lost: the seed list is sized from the count
+ *                  when it outgrows its capacity.  SP_ENOMEM names the size that did not fit.
+ *   sp_ltr_hsps    the list of the last sp_ltr_seeds; n = its n_hsps
+ *   sp_ltr_detect_set_chunk     starts a chunk of a chromosome owns (1 .. 2^24 - 32800; 0 = that default); tests use
+ *                  small values so that small inputs span many chunks -- no result depends on it
+ *   sp_ltr_detect_set_capacity  seeds the append list holds at first (0 = the default, 2^20); no result depends on it
+ * SP_EINVAL: null arguments, a chromosome out of range or without a packed sequence, dmin < 1 or dmin > dmax, xdrop < 0,
+ * maxlen < 1, an n that is not the last call's.  SP_EUNSUP: seed_len outside 12..20, dmax > 32767, maxlen > 8192
+ * (SP_LA_MAXLEN), a chromosome above 2^31 - 16 bases.                                                              */
+int sp_ltr_seeds(sp_ctx *ctx, int chrom, int seed_len, int xdrop, int64_t dmin, int64_t dmax, int32_t maxlen,
+                 int64_t *n_seeds, int64_t *n_hsps);
+int sp_ltr_hsps(sp_ctx *ctx, int32_t *p0, int32_t *len, int32_t *d, int64_t n);
+int sp_ltr_detect_set_chunk(sp_ctx *ctx, int64_t body_bases);
+int sp_ltr_detect_set_capacity(sp_ctx *ctx, int64_t seeds);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

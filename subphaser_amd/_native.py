@@ -35,7 +35,7 @@ SYMBOLS = [
     "sp_labels_set", "sp_labels_set_device", "sp_map_nslots", "sp_map_bins", "sp_map_bins_all", "sp_stack_windows", "sp_stack_windows_dev", "sp_stack_enrich", "sp_map_features", "sp_map_intervals", "sp_labels_hit",
     "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_ranktest_wide", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
-    "sp_ltr_align",
+    "sp_ltr_align", "sp_ltr_seeds", "sp_ltr_hsps", "sp_ltr_detect_set_chunk", "sp_ltr_detect_set_capacity",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -137,6 +137,10 @@ def load():
     L.sp_blocks_release.argtypes = [vp, ci]
     L.sp_blocks_set_cells.argtypes = [vp, ci]
     L.sp_ltr_align.argtypes = [vp, i64, vp, vp, vp, vp, vp, ci, vp]
+    L.sp_ltr_seeds.argtypes = [vp, ci, ci, ci, i64, i64, C.c_int32, P(i64), P(i64)]
+    L.sp_ltr_hsps.argtypes = [vp, vp, vp, vp, i64]
+    L.sp_ltr_detect_set_chunk.argtypes = [vp, i64]
+    L.sp_ltr_detect_set_capacity.argtypes = [vp, i64]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -973,6 +977,31 @@ class Context:
         out = np.zeros((n, 6), np.int32)
         self._ck(self.L.sp_ltr_align(self.h, n, _p(chrom), _p(a_start), _p(a_len), _p(b_start), _p(b_len), int(band), _p(out)))
         return out
+
+    def ltr_seeds(self, chrom, seed_len, xdrop, dmin, dmax, maxlen):
+        """De novo LTR detection on one chromosome (sp_ltr_seeds; definition in csrc/sp_ltrdetect.h): exact seeds of
+        seed_len bases at a distance dmin..dmax, extended without gaps under the X-drop.  Returns (n_seeds, n_hsps) and
+        keeps the HSP list for ltr_hsps."""
+        ns, nh = C.c_int64(), C.c_int64()
+        self._ck(self.L.sp_ltr_seeds(self.h, int(chrom), int(seed_len), int(xdrop), int(dmin), int(dmax), int(maxlen), C.byref(ns), C.byref(nh)))
+        return ns.value, nh.value
+
+    def ltr_hsps(self, n):
+        """The n = n_hsps HSPs of the last ltr_seeds, distinct and ascending as tuples: (p0 int32, len int32, d int32) --
+        the copies are [p0, p0 + len) and [p0 + d, p0 + d + len), 0-based."""
+        p0, ln, d = np.empty(int(n), np.int32), np.empty(int(n), np.int32), np.empty(int(n), np.int32)
+        self._ck(self.L.sp_ltr_hsps(self.h, _p(p0), _p(ln), _p(d), int(n)))
+        return p0, ln, d
+
+    def ltr_detect_set_chunk(self, bases=0):
+        """starts of a chromosome that one chunk of the detection owns (0: the default); a small value makes small inputs
+        span many chunks; results do not depend on it"""
+        self._ck(self.L.sp_ltr_detect_set_chunk(self.h, int(bases)))
+
+    def ltr_detect_set_capacity(self, seeds=0):
+        """seeds the detection's append list holds before it is sized from the count (0: the default); results do not
+        depend on it"""
+        self._ck(self.L.sp_ltr_detect_set_capacity(self.h, int(seeds)))
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

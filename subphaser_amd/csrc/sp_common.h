@@ -85,6 +85,7 @@ struct sp_tabref {
 };
 
 struct sp_blocks_state;   // sp_blocks.hip
+struct sp_ltrdetect_state;   // sp_ltrdetect.hip
 
 // The label set of sp_labels_set: `kind` says which buffers hold it (sp_labelplan.h), bb / ovf_mask describe a bucket
 // table.  `ready` is cleared on entry to the table build and by sp_count whenever k changes, and set only when
@@ -214,6 +215,7 @@ struct sp_ctx {
     sp_buf b_hc;            // heatmap clustering: points, the P x P distance matrix, merges, chain state (sp_hclust.hip)
     sp_buf b_wtab, b_enr;   // window table (device) and the enrichment outputs
     sp_blocks_state *blocks = nullptr;   // per-chromosome single-copy k-mer indexes of the block stage (sp_blocks.hip)
+    sp_ltrdetect_state *ltrdetect = nullptr;   // chunk size, seed capacity and the last HSP list of the LTR detection (sp_ltrdetect.hip)
     sp_buf b_fq;      // global slow queue of the filter
     sp_buf b_fflat;   // flat set tables of the filter (sp_filter.hip)
     sp_buf b_map, b_mapdesc, b_ival, b_emit, b_fpar, b_win;  // reusable device buffers of sp_map_bins / k3_emit / sp_filter / stack

@@ -154,6 +154,7 @@ int sp_ctx_destroy(sp_ctx *ctx) {
     free_filter(ctx);
     sp_sparse_release(ctx);
     sp_blocks_destroy(ctx);
+    sp_ltrdetect_destroy(ctx);
     if (ctx->d_label) hipFree(ctx->d_label);
     if (ctx->d_bloom) hipFree(ctx->d_bloom);
     if (ctx->d_scratch) hipFree(ctx->d_scratch);

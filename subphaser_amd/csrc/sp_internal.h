@@ -68,5 +68,8 @@ int sp_tw_means_launch(sp_ctx *ctx, const sp_tw_plan &plan, int *d_poff, uint8_t
 void sp_blocks_drop(sp_ctx *ctx, int chrom);
 void sp_blocks_destroy(sp_ctx *ctx);
 
+// sp_ltrdetect.hip: everything at sp_ctx_destroy
+void sp_ltrdetect_destroy(sp_ctx *ctx);
+
 // sp_map.hip
 int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n);

@@ -7,7 +7,11 @@ onto the elements, tests them for enrichment and dates the enriched ones from th
 supplies and uses every record of it, as the reference does under -all_ltr.  What this module restates is the record
 (fields, derived coordinates, id), the overlap resolution for records without a classification, the age arithmetic and
 the `.ltr.insert.data` / `.ltr.insert.summary` writers; the similarity is computed from the resident genome by
-Context.ltr_align (csrc/sp_ltralign.h) unless -ltr_identity scn asks for the file's."""
+Context.ltr_align (csrc/sp_ltralign.h) unless -ltr_identity scn asks for the file's.
+
+Under -ltr_denovo the `.scn` is written here instead of read: Context.ltr_seeds / ltr_hsps give the extended exact seeds of
+a chromosome (csrc/sp_ltrdetect.h), chain_hsps joins them into chains, candidates keeps the chains that look like an
+LTR pair, similarity filters them by the alignment of the two LTRs and write_scn writes the 12 columns."""
 import math
 
 import numpy as np
@@ -16,6 +20,10 @@ from ._native import LTR_ALIGN_BAND as FLAG_BAND, LTR_ALIGN_EDGE as FLAG_EDGE, L
 from .runtime import logger
 
 LTR_BAND = 64
+# detection: the values the reference passes to its detectors (LTR.py:39-41: -seed 20 -minlenltr 100 -maxlenltr 7000
+# -mindistltr 1000 -maxdistltr 15000 -xdrop ... -similar 85), and the two of the chaining.  Provisional, as LTR_BAND is.
+LTR_SEED, LTR_MINDIST, LTR_MAXDIST, LTR_MINLEN, LTR_MAXLEN, LTR_XDROP, LTR_SIMILAR = 20, 1000, 15000, 100, 7000, 20, 85.0
+LTR_CHAIN_INDEL, LTR_CHAIN_JOIN = 32, 200
 IDENTITY_MODES = ("align", "scn")
 MAX_OVL = 10
 
@@ -36,6 +44,17 @@ class Record:
         self.element_len, self.start, self.lltr = int(fields[2]), int(fields[3]), int(fields[5])
         self.end, self.rltr = int(fields[7]), int(fields[8])
         self.similarity, self.seq_nr, self.seq_id = float(fields[9]), int(fields[10]), fields[11]
+
+    @classmethod
+    def from_coords(cls, seq_id, seq_nr, a0, a1, b0, b1, similarity):
+        """the record of the LTRs [a0, a1) and [b0, b1), 0-based; the similarity keeps the two decimals a `.scn` holds"""
+        f = [a0 + 1, b1, b1 - a0, a0 + 1, a1, a1 - a0, b0 + 1, b1, b1 - b0, "%.2f" % similarity, seq_nr, seq_id]
+        return cls([str(x) for x in f])
+
+    def columns(self):
+        """the 12 columns of the record's line"""
+        return [self.start, self.end, self.element_len, self.start, self.lltr_e, self.lltr, self.rltr_s, self.end, self.rltr,
+                "%.2f" % self.similarity, self.seq_nr, self.seq_id]
 
     @property
     def lltr_e(self):
@@ -67,6 +86,70 @@ def read_scn(path):
                 continue
             out.append(Record(line.strip().split(), "{}:{}".format(path, ln)))
     return out
+
+
+SCN_HEADER = ("# LTR-RT candidates of the de novo detection (-ltr_denovo): chained exact seeds, no TSD or motif search\n"
+              "# predictions are reported in the following way\n"
+              "# s(ret) e(ret) l(ret) s(lLTR) e(lLTR) l(lLTR) s(rLTR) e(rLTR) l(rLTR) sim(LTRs) seq-nr chr\n"
+              "# where:\n# s = starting position\n# e = ending position\n# l = length\n# ret = LTR-retrotransposon\n"
+              "# lLTR = left LTR\n# rLTR = right LTR\n# sim = similarity\n# seq-nr = sequence number\n")
+
+
+def write_scn(fout, ltrs, source="device"):
+    """the comment header of ltrharvest's output as the reference's tmp/LTR.scn carries it, then the 12 columns of every
+    record, 1-based and inclusive, and a `#source` column behind them, which read_scn ignores"""
+    fout.write(SCN_HEADER)
+    for r in ltrs:
+        fout.write(" ".join(map(str, r.columns())) + " #" + source + "\n")
+
+
+def chain_hsps(hsps, indel=LTR_CHAIN_INDEL, join=LTR_CHAIN_JOIN):
+    """Chains of the HSPs (p0, n, d) of one chromosome, walked in ascending order: [(a0, a1, b0, b1)] in the order the chains
+    were opened.  A chain keeps the hull of its left copies [a0, a1) and of its right copies [b0, b1), `end` = the largest
+    p0 + n so far and the d, p0, q0 of its last HSP; it closes for good once an HSP arrives with p0 - end > join.  An HSP
+    joins an open chain when |d - last d| <= indel, p0 >= last p0, p0 + d >= last q0 and p0 + n > end -- of the chains
+    that qualify the one with the largest end, the earliest opened on a tie -- else it opens a chain."""
+    chains, live = [], []          # a chain: [a0, a1, b0, b1, end, d, p0, q0]; live: indices of the open ones, by opening
+    for p0, n, d in hsps:
+        p0, n, d = int(p0), int(n), int(d)
+        live = [i for i in live if p0 - chains[i][4] <= join]
+        best = None
+        for i in live:
+            c = chains[i]
+            if abs(d - c[5]) <= indel and p0 >= c[6] and p0 + d >= c[7] and p0 + n > c[4] and (best is None or c[4] > chains[best][4]):
+                best = i
+        if best is None:
+            live.append(len(chains))
+            chains.append([p0, p0 + n, p0 + d, p0 + d + n, p0 + n, d, p0, p0 + d])
+        else:
+            c = chains[best]
+            c[1], c[3], c[4] = max(c[1], p0 + n), max(c[3], p0 + d + n), max(c[4], p0 + n)
+            c[5], c[6], c[7] = d, p0, p0 + d
+    return [tuple(c[:4]) for c in chains]
+
+
+def candidates(chains, minlen=LTR_MINLEN, maxlen=LTR_MAXLEN, dmin=LTR_MINDIST, dmax=LTR_MAXDIST):
+    """the chains that look like the two LTRs of an element: both hulls minlen..maxlen long, their starts dmin..dmax apart,
+    the left one ending before the right one begins"""
+    return [(a0, a1, b0, b1) for a0, a1, b0, b1 in chains
+            if minlen <= a1 - a0 <= maxlen and minlen <= b1 - b0 <= maxlen and dmin <= b0 - a0 <= dmax and a1 <= b0]
+
+
+def similarity(counts, similar=LTR_SIMILAR):
+    """(sim per candidate or None, indices kept, number dropped as not aligned) from the int32 [n, 6] of Context.ltr_align:
+    sim = 100 match / (match + mismatch + gap) -- skip columns do not count; a candidate outside the limits of the alignment
+    (FLAG_BAND, FLAG_LEN) or without a counted column is dropped; one with sim >= similar is kept"""
+    sims, keep, dropped = [], [], 0
+    for i, row in enumerate(counts):
+        m, x, g, flags = int(row[1]), int(row[2]), int(row[3]), int(row[5])
+        if flags & (FLAG_BAND | FLAG_LEN) or m + x + g == 0:
+            sims.append(None)
+            dropped += 1
+            continue
+        sims.append(100 * m / (m + x + g))
+        if sims[-1] >= similar:
+            keep.append(i)
+    return sims, keep, dropped
 
 
 def resolve_overlaps(ltrs, max_ovl=MAX_OVL):

@@ -18,8 +18,10 @@ runs unless -just_core, -disable_circos or -disable_blocks is given.
 Of module 3 the part that needs no detector is here: stage_ltr takes LTR-RT coordinates from -ltr_scn (the `.scn` the
 reference's LTR step writes), maps the subgenome-specific k-mers onto the elements of the resident genome, writes
 `.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data` / `.summary` and the two age figures; the
-divergence of an element's two LTRs comes from a banded alignment on the device (ltr.py, csrc/sp_ltralign.hip).  LTR
-detection, TEsorter, the LTR trees and the circos figure itself stay with the reference.
+divergence of an element's two LTRs comes from a banded alignment on the device (ltr.py, csrc/sp_ltralign.hip).  With
+-ltr_denovo instead of -ltr_scn the coordinates are detected on the resident genome first (csrc/sp_ltrdetect.hip: exact
+seeds, gapless extension; ltr.py: chaining) and written as `.ltr.scn`.  ltr_finder / ltrharvest themselves, TEsorter, the
+LTR trees and the circos figure itself stay with the reference.
 """
 import argparse
 import io
@@ -123,8 +125,8 @@ CLI = [
                                help="windows a block may skip, and drift off its diagonal, between two called windows")),
     ]),
     ("LTR", "subgenome-specific LTR-RTs and their insertion ages from LTR-RT coordinates (the reference's module 3 without "
-            "detection, TEsorter and the LTR trees): the stage runs when -ltr_scn is given, unless -just_core or -disable_ltr; "
-            "every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured", [
+            "TEsorter and the LTR trees): the stage runs when -ltr_scn or -ltr_denovo is given, unless -just_core or "
+            "-disable_ltr; every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured", [
         (("-ltr_scn",), dict(type=str, metavar="FILE", default=None,
                              help="LTR-RTs in the 12-column format of the reference's tmp/LTR.scn (ltrharvest's columns plus the "
                                   "sequence id)")),
@@ -133,6 +135,23 @@ CLI = [
                                        "mismatch / (match + mismatch)) or scn (1 - similarity / 100 of the file, as the reference)")),
         (("-ltr_band",), dict(type=int, metavar="INT", default=ltr_mod.LTR_BAND,
                               help="diagonals either side of the band of the LTR alignment; provisional: judged on synthetic pairs only")),
+        (("-ltr_denovo",), dict(help="detect the LTR-RTs on the GPU (exact seeds at a bounded distance, gapless X-drop extension, "
+                                     "chaining; no TSD or motif search) and write them to `.ltr.scn`; not with -ltr_scn.  The "
+                                     "defaults of the -ltr_* options below are the values the reference passes to its detectors "
+                                     "and are provisional: judged on synthetic genomes only, never against ltrharvest or "
+                                     "ltr_finder", **_FLAG)),
+        (("-ltr_seed",), dict(type=int, metavar="INT", default=ltr_mod.LTR_SEED, help="length of the exact seed, 12..20")),
+        (("-ltr_mindist",), dict(type=int, metavar="INT", default=ltr_mod.LTR_MINDIST, help="smallest distance between the starts of the two LTRs")),
+        (("-ltr_maxdist",), dict(type=int, metavar="INT", default=ltr_mod.LTR_MAXDIST, help="largest such distance, at most 32767")),
+        (("-ltr_minlen",), dict(type=int, metavar="INT", default=ltr_mod.LTR_MINLEN, help="shortest LTR")),
+        (("-ltr_maxlen",), dict(type=int, metavar="INT", default=ltr_mod.LTR_MAXLEN, help="longest LTR, at most 8192")),
+        (("-ltr_xdrop",), dict(type=int, metavar="INT", default=ltr_mod.LTR_XDROP, help="X-drop of the gapless extension (+2 / -2)")),
+        (("-ltr_similar",), dict(type=float, metavar="FLOAT", default=ltr_mod.LTR_SIMILAR,
+                                 help="minimum similarity of the two LTRs in percent: match / (match + mismatch + gap) of their alignment")),
+        (("-ltr_chain_indel",), dict(type=int, metavar="INT", default=ltr_mod.LTR_CHAIN_INDEL,
+                                     help="chaining: largest shift of the diagonal between two extended seeds")),
+        (("-ltr_chain_join",), dict(type=int, metavar="INT", default=ltr_mod.LTR_CHAIN_JOIN,
+                                    help="chaining: largest distance of an extended seed from the end of its chain")),
     ]),
     ("Other options", None, [
         (("-p", "-ncpu"), dict(dest="ncpu", type=int, metavar="INT", default=NCPU)),
@@ -167,6 +186,8 @@ def makeArgparse(argv=None):
     parser.add_argument("-v", "-version", action="version",
                         version="subphaser_amd {} (interface of SubPhaser {})".format(__version__, REFERENCE_VERSION))
     args = parser.parse_args(argv)
+    if args.ltr_denovo and args.ltr_scn:
+        parser.error("-ltr_denovo detects the LTR-RTs, -ltr_scn reads them from a file: give one of the two")
     if args.prefix is not None:          # the prefix goes in front of directory names AND file names (__main__.py:242-245)
         args.prefix = args.prefix.replace("/", "_")
         args.outdir, args.tmpdir = args.prefix + args.outdir, args.prefix + args.tmpdir
@@ -652,10 +673,57 @@ class Pipeline:
                 logger.warning("blocks not plotted: {}".format(e))
         self._background.append((fig, lambda: None, done))
 
-    # ---- stage 7: LTR-RTs from a .scn -------------------------------------------------------------------------
+    # ---- stage 7: LTR-RTs from a .scn, or detected -----------------------------------------------------------
+    def _ltr_detect(self, lay, labels, ctx, band):
+        """-ltr_denovo: the LTR-RT candidates of every chromosome, written to `.ltr.scn` -- per chromosome the extended seeds
+        of the device (Context.ltr_seeds / ltr_hsps) chained on the host, then one ltr_align call for all candidates and the
+        similarity filter (ltr.py).  There is no CPU detector: a context without ltr_seeds is an error."""
+        if not (hasattr(ctx, "ltr_seeds") and hasattr(ctx, "ltr_hsps") and hasattr(ctx, "ltr_align")):
+            raise RuntimeError("-ltr_denovo needs a context with ltr_seeds, ltr_hsps and ltr_align (libsubphaser_hip.so); there is "
+                               "no CPU detector: pass -ltr_scn FILE instead")
+        opt = {name: getattr(self, "ltr_" + name, default) for name, default in (
+            ("seed", ltr_mod.LTR_SEED), ("mindist", ltr_mod.LTR_MINDIST), ("maxdist", ltr_mod.LTR_MAXDIST), ("minlen", ltr_mod.LTR_MINLEN),
+            ("maxlen", ltr_mod.LTR_MAXLEN), ("xdrop", ltr_mod.LTR_XDROP), ("similar", ltr_mod.LTR_SIMILAR),
+            ("chain_indel", ltr_mod.LTR_CHAIN_INDEL), ("chain_join", ltr_mod.LTR_CHAIN_JOIN))}
+        if not 1 <= opt["minlen"] <= opt["maxlen"]:
+            raise ValueError("-ltr_minlen {} is below 1 or above -ltr_maxlen {}".format(opt["minlen"], opt["maxlen"]))
+        if opt["chain_indel"] < 0 or opt["chain_join"] < 0:
+            raise ValueError("-ltr_chain_indel {} or -ltr_chain_join {} is below 0".format(opt["chain_indel"], opt["chain_join"]))
+        logger.info("Detecting LTR-RTs: seed {seed}, distance {mindist}-{maxdist}, LTR length {minlen}-{maxlen}, X-drop {xdrop}, "
+                    "similarity >= {similar}, chaining {chain_indel} / {chain_join}; no TSD or motif search".format(**opt))
+        t0 = time.perf_counter()
+        n_seeds = n_hsps = n_chains = 0
+        cands = []                     # (chromosome index, a0, a1, b0, b1)
+        for ci in range(len(labels)):
+            ns, nh = ctx.ltr_seeds(ci, opt["seed"], opt["xdrop"], opt["mindist"], opt["maxdist"], opt["maxlen"])
+            p0, ln, d = ctx.ltr_hsps(nh)
+            chains = ltr_mod.chain_hsps(zip(p0.tolist(), ln.tolist(), d.tolist()), opt["chain_indel"], opt["chain_join"])
+            n_seeds, n_hsps, n_chains = n_seeds + ns, n_hsps + nh, n_chains + len(chains)
+            cands += [(ci,) + c for c in ltr_mod.candidates(chains, opt["minlen"], opt["maxlen"], opt["mindist"], opt["maxdist"])]
+        logger.info("{} seeds, {} extended seeds (HSPs), {} chains, {} candidates on {} chromosomes in {:.2f} s".format(
+            n_seeds, n_hsps, n_chains, len(cands), len(labels), time.perf_counter() - t0))
+        ltrs = []
+        if cands:
+            t0 = time.perf_counter()
+            ci, a0, a1, b0, b1 = (np.array(x, np.int64) for x in zip(*cands))
+            counts = np.asarray(ctx.ltr_align(ci.astype(np.int32), a0, a1 - a0, b0, b1 - b0, band))
+            sims, keep, dropped = ltr_mod.similarity(counts, opt["similar"])
+            if dropped:
+                logger.info("{} candidates outside the limits of the alignment (band {}) or without an aligned column: dropped".format(dropped, band))
+            ltrs = [ltr_mod.Record.from_coords(labels[cands[i][0]], cands[i][0], *cands[i][1:], sims[i]) for i in keep]
+            logger.info("{} candidates aligned (band {}) in {:.2f} s; {} with similarity >= {}".format(
+                len(cands), band, time.perf_counter() - t0, len(ltrs), opt["similar"]))
+        scn = lay.out("ltr.scn")
+        with open(scn, "w") as fout:
+            ltr_mod.write_scn(fout, ltrs)
+        mk_ckp(lay.ckp(scn))
+        logger.info("{} LTR-RTs detected, written to `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
+        return ltrs, scn
+
     def stage_ltr(self, lay, labels, cl, kmer_labels):
         """`.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data`, `.ltr.insert.summary` and the two age
-        figures from the LTR-RTs of -ltr_scn (step_ltr, __main__.py:549-620, without detection and classification)."""
+        figures from the LTR-RTs of -ltr_scn (step_ltr, __main__.py:549-620, without detection and classification), or from
+        those -ltr_denovo detects and writes to `.ltr.scn`."""
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             logger.info("LTR stage skipped: it runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
             return
@@ -665,8 +733,12 @@ class Pipeline:
         band = int(getattr(self, "ltr_band", ltr_mod.LTR_BAND))
         if band < 0:
             raise ValueError("-ltr_band {} is below 0".format(band))
-        ltrs = ltr_mod.read_scn(self.ltr_scn)
-        logger.info("{} LTRs read from `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), self.ltr_scn))
+        scn = getattr(self, "ltr_scn", None)
+        if getattr(self, "ltr_denovo", False) and not scn:
+            ltrs, scn = self._ltr_detect(lay, labels, ctx, band)
+        else:
+            ltrs = ltr_mod.read_scn(scn)
+            logger.info("{} LTRs read from `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
         aliases, index = dict(getattr(self, "d_targets", None) or {}), {lab: i for i, lab in enumerate(labels)}
         known = []
         for r in ltrs:
@@ -679,7 +751,7 @@ class Pipeline:
         for r in known:
             if not (1 <= r.start and r.lltr >= 1 and r.rltr >= 1 and r.lltr_e <= r.end and r.start <= r.rltr_s and r.end <= lengths[index[r.seq_id]]):
                 raise ValueError("{}: LTR-RT {} does not lie on its chromosome (length {}) or its LTRs (lengths {}, {}) do not lie in it".format(
-                    self.ltr_scn, r.id, lengths[index[r.seq_id]], r.lltr, r.rltr))
+                    scn, r.id, lengths[index[r.seq_id]], r.lltr, r.rltr))
         n_known = len(known)
         ltrs = ltr_mod.group_resolve_overlaps(known)
         logger.info("After filtering, {} / {} ({:.1%}) LTRs retained".format(len(ltrs), n_known, len(ltrs) / max(1, n_known)))
@@ -688,7 +760,7 @@ class Pipeline:
         chrom = np.array([index[r.seq_id] for r in ltrs], np.int32)
         st, en = np.array([r.start for r in ltrs], np.int64), np.array([r.end for r in ltrs], np.int64)
         if len(ltrs) and int((en - st).max()) > FEATURE_BIN:
-            raise ValueError("{}: an LTR-RT of {} bases is longer than a {}-base bin".format(self.ltr_scn, int((en - st).max()), FEATURE_BIN))
+            raise ValueError("{}: an LTR-RT of {} bases is longer than a {}-base bin".format(scn, int((en - st).max()), FEATURE_BIN))
         ctx.labels_set(kmer_labels.keys, kmer_labels.sg_idx, S)
         counts = np.asarray(ctx.map_intervals(chrom, st, en), np.int64).reshape(len(ltrs), S) if len(ltrs) else np.zeros((0, S), np.int64)
         hit = np.flatnonzero(counts.sum(axis=1) > 0).tolist()
@@ -793,10 +865,15 @@ class Pipeline:
                 self.stage_features(lay, cl, kmer_labels)
             if not (self.disable_circos or self.disable_blocks):
                 self.stage_blocks(lay, labels, d_size, cl)
-            ran_ltr = bool(getattr(self, "ltr_scn", None)) and not self.disable_ltr
+            denovo = bool(getattr(self, "ltr_denovo", False)) and not getattr(self, "ltr_scn", None)
+            ran_ltr = (bool(getattr(self, "ltr_scn", None)) or denovo) and not self.disable_ltr
             if ran_ltr:
                 self.stage_ltr(lay, labels, cl, kmer_labels)
-            if ran_ltr:
+            if ran_ltr and denovo:
+                logger.info("Of modules 3-4, TEsorter classification, the LTR trees and the circos figure are not part of this build "
+                            "(the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's); run the reference on "
+                            "the outputs above for them")
+            elif ran_ltr:
                 logger.info("Of modules 3-4, LTR detection, TEsorter classification, the LTR trees and the circos figure are not "
                             "part of this build; run the reference on the outputs above for them")
             elif not (self.disable_ltr and self.disable_circos):
