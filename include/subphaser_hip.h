@@ -447,6 +447,40 @@ int sp_ltr_hsps(sp_ctx *ctx, int32_t *p0, int32_t *len, int32_t *d, int64_t n);
 int sp_ltr_detect_set_chunk(sp_ctx *ctx, int64_t body_bases);
 int sp_ltr_detect_set_capacity(sp_ctx *ctx, int64_t seeds);
 
+/* ---- LTR-RT tree: MinHash sketches, their pairwise comparison, neighbour joining ------
+ * The tree of the LTR stage is defined by integer arithmetic (csrc/sp_ltrtree.h holds the definition: k-mer, hash, sketch,
+ * pair, criterion, tie order, update, guard); the distance between (shared, denom) and the matrix is host arithmetic.
+ *   sp_ltr_sketch        bottom-s sketches of n elements [start[i], end[i]) (0-based, half-open) of chromosome chrom[i] on
+ *                        the genome of sp_genome_add: sketch n x s uint64 (ascending, unused entries UINT64_MAX) and len n
+ *                        int32, caller-owned host memory.  k odd in 9..31, s in 16..4096, end - start <= 65536.  One
+ *                        workgroup per element, longest first.  n = 0 is fine.
+ *   sp_ltr_sketch_set_chunk  starts of an element that one chunk of the kernel holds (1..4096; 0 = the default, which
+ *                        depends on s); tests use small values so that short elements span many chunks -- no result depends
+ *                        on it
+ *   sp_ltr_sketch_pairs  (shared, denom) of all n x n pairs of n sketches in host memory (hand-made ones are fine: rows
+ *                        ascending and distinct in their first len[i] entries); both matrices n x n int32, written in full:
+ *                        symmetric, the diagonal is (len, len).  At most 32 MiB of sketches (n * s * 8 bytes) go up.
+ *   sp_nj_tree           neighbour joining on the N x N int64 matrix `dist` (host): merges (N - 1) x 5 int64 =
+ *                        (i, j, D(i, j), R_i, R_j) per join and (i, j, D(i, j), 0, 0) for the last two slots.  2 <= N <= 4096.
+ *   sp_nj_set_mode       which driver runs the joins: 0 = chosen by N (the default), 1 = one workgroup that loops, 2 = one
+ *                        row-minimum launch and one join launch per join.  No result depends on it.
+ *   sp_nj_set_guard      the magnitude at which a derived distance stops the run with SP_ESTATE: 1 .. 2^40, 0 = the
+ *                        default 2^40.  For tests: no matrix inside the input contract is known to reach 2^40, so a small
+ *                        value is how the guard's path is reached.  A limit that is not reached changes no result.
+ * SP_EINVAL: a NULL pointer; no genome; a chromosome out of range; an interval off its chromosome or with end <= start; k
+ * or s out of range; len[i] outside 0..s; N < 2; a matrix that is asymmetric, has a non-zero diagonal or an entry outside
+ * [0, 2^31) -- all checked on the host before any launch.  SP_EUNSUP: an element above 65536 bases, more than 32 MiB of
+ * sketches, N > 4096 -- decided before any allocation.  SP_ENOMEM: the workspace does not fit.  SP_ESTATE: a derived
+ * distance reached the guard (2^40, sp_ltrtree.h; sp_nj_set_guard) in magnitude; `merges` is then undefined.                          */
+int sp_ltr_sketch(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int k, int s,
+                  uint64_t *sketch, int32_t *len);
+int sp_ltr_sketch_set_chunk(sp_ctx *ctx, int starts);
+int sp_ltr_sketch_pairs(sp_ctx *ctx, int n, int s, const uint64_t *sketch, const int32_t *len, int32_t *shared,
+                        int32_t *denom);
+int sp_nj_tree(sp_ctx *ctx, const int64_t *dist, int N, int64_t *merges);
+int sp_nj_set_mode(sp_ctx *ctx, int mode);
+int sp_nj_set_guard(sp_ctx *ctx, int64_t limit);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

@@ -24,6 +24,7 @@ RANKTEST_METHODS = ("kruskal", "mannwhitneyu")     # SP_RT_KRUSKAL, SP_RT_MWU: t
 BLOCKS_K_RANGE, BLOCKS_MAX_SAMPLE = (17, 31), 16   # SP_BK_KMIN, SP_BK_KMAX (odd only), SP_BK_SMAX in csrc/sp_blocks.h
 LTR_ALIGN_MAXLEN, LTR_ALIGN_MAXBAND = 8192, 1024    # SP_LA_MAXLEN, SP_LA_MAXBAND in csrc/sp_ltralign.h
 LTR_ALIGN_EDGE, LTR_ALIGN_BAND, LTR_ALIGN_LEN = 1, 2, 4   # SP_LA_F_*: the flag bits of ltr_align's last column
+LTRTREE_MAX_LEN, LTRTREE_MAX_N = 65536, 4096       # SP_LT_MAXLEN, SP_LT_MAXN in csrc/sp_ltrtree.h
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
@@ -36,6 +37,7 @@ SYMBOLS = [
     "sp_enrich", "sp_enrich_dev", "sp_kmer_ttest", "sp_kmer_ttest_wide", "sp_kmer_ranktest", "sp_kmer_ranktest_wide", "sp_kmer_wilcoxon", "sp_kmeans_bootstrap", "sp_kmer_pca_gram", "sp_kmer_pca_signs", "sp_hclust_complete",
     "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
     "sp_ltr_align", "sp_ltr_seeds", "sp_ltr_hsps", "sp_ltr_detect_set_chunk", "sp_ltr_detect_set_capacity",
+    "sp_ltr_sketch", "sp_ltr_sketch_set_chunk", "sp_ltr_sketch_pairs", "sp_nj_tree", "sp_nj_set_mode", "sp_nj_set_guard",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -141,6 +143,12 @@ def load():
     L.sp_ltr_hsps.argtypes = [vp, vp, vp, vp, i64]
     L.sp_ltr_detect_set_chunk.argtypes = [vp, i64]
     L.sp_ltr_detect_set_capacity.argtypes = [vp, i64]
+    L.sp_ltr_sketch.argtypes = [vp, i64, vp, vp, vp, ci, ci, vp, vp]
+    L.sp_ltr_sketch_set_chunk.argtypes = [vp, ci]
+    L.sp_ltr_sketch_pairs.argtypes = [vp, ci, ci, vp, vp, vp, vp]
+    L.sp_nj_tree.argtypes = [vp, vp, ci, vp]
+    L.sp_nj_set_mode.argtypes = [vp, ci]
+    L.sp_nj_set_guard.argtypes = [vp, i64]
     L.sp_sparse_sizes.argtypes = [vp, vp]
     L.sp_sparse_sample.argtypes = [vp, ci, i64, vp, P(i64)]
     L.sp_sparse_split.argtypes = [vp, ci, vp, ci, vp]
@@ -1002,6 +1010,59 @@ class Context:
         """seeds the detection's append list holds before it is sized from the count (0: the default); results do not
         depend on it"""
         self._ck(self.L.sp_ltr_detect_set_capacity(self.h, int(seeds)))
+
+    # -------------------------------------------------------------- LTR tree
+    def ltr_sketch(self, chrom, start, end, k, s):
+        """Bottom-s MinHash sketches of the elements [start, end) (0-based, half-open) on the resident genome
+        (sp_ltr_sketch; definition in csrc/sp_ltrtree.h): (sketch uint64 [n, s], ascending with UINT64_MAX behind the
+        last hash, len int32 [n]).  k odd in 9..31, s in 16..4096, elements of up to LTRTREE_MAX_LEN bases."""
+        chrom = np.ascontiguousarray(chrom, np.int32)
+        start, end = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+        n = int(chrom.size)
+        if start.size != n or end.size != n:
+            raise ValueError("chrom, start and end must have one entry per element")
+        sketch, ln = np.empty((n, max(int(s), 0)), np.uint64), np.empty(n, np.int32)
+        self._ck(self.L.sp_ltr_sketch(self.h, n, _p(chrom), _p(start), _p(end), int(k), int(s), _p(sketch), _p(ln)))
+        return sketch, ln
+
+    def ltr_sketch_set_chunk(self, starts=0):
+        """starts of an element that one chunk of the sketch kernel holds (0: the default); a small value makes short
+        elements span many chunks; results do not depend on it"""
+        self._ck(self.L.sp_ltr_sketch_set_chunk(self.h, int(starts)))
+
+    def ltr_sketch_pairs(self, sketch, length):
+        """(shared, denom), int32 [n, n] each, of all pairs of the n sketches (sp_ltr_sketch_pairs): the merge of two
+        ascending lists is walked until min(s, |A u B|) distinct values are consumed."""
+        sketch = np.ascontiguousarray(sketch, np.uint64)
+        length = np.ascontiguousarray(length, np.int32)
+        if sketch.ndim != 2 or length.size != sketch.shape[0]:
+            raise ValueError("sketch must be n x s and length must have n entries")
+        n, s = sketch.shape
+        shared, denom = np.empty((n, n), np.int32), np.empty((n, n), np.int32)
+        self._ck(self.L.sp_ltr_sketch_pairs(self.h, int(n), int(s), _p(sketch), _p(length), _p(shared), _p(denom)))
+        return shared, denom
+
+    def nj_tree(self, dist):
+        """Neighbour joining on a symmetric int64 [N, N] matrix with zero diagonal and entries in [0, 2^31)
+        (sp_nj_tree): int64 [N - 1, 5] records (i, j, D(i, j), R_i, R_j), the last one (i, j, D(i, j), 0, 0).
+        ValueError when the matrix is not such a matrix, N is outside 2..LTRTREE_MAX_N, or the guard fires."""
+        dist = np.ascontiguousarray(dist, np.int64)
+        if dist.ndim != 2 or dist.shape[0] != dist.shape[1]:
+            raise ValueError("dist must be N x N")
+        N = int(dist.shape[0])
+        merges = np.empty((max(N - 1, 0), 5), np.int64)
+        self._ck(self.L.sp_nj_tree(self.h, _p(dist), N, _p(merges)))
+        return merges
+
+    def nj_set_mode(self, mode=0):
+        """which driver runs the joins of nj_tree: 0 by size, 1 the looping workgroup, 2 two launches per join; results
+        do not depend on it"""
+        self._ck(self.L.sp_nj_set_mode(self.h, int(mode)))
+
+    def nj_set_guard(self, limit=0):
+        """the magnitude at which a derived distance of nj_tree stops the run (ValueError): 1 .. 2^40, 0 the default 2^40;
+        for tests -- a limit that is not reached changes no result"""
+        self._ck(self.L.sp_nj_set_guard(self.h, int(limit)))
 
     def stage_rows(self, counts):
         """Copy a uint32 [M, C] matrix to a device buffer owned by the context (one at a time; the previous one is

@@ -213,6 +213,10 @@ struct sp_ctx {
     sp_buf b_kb;            // k-means bootstrap: columns, labels, iteration counts, Gram copies (sp_kboot.hip)
     sp_buf b_kp;            // k-mer PCA: lengths, row statistics, chunk partials, sign candidates (sp_kpca.hip)
     sp_buf b_hc;            // heatmap clustering: points, the P x P distance matrix, merges, chain state (sp_hclust.hip)
+    sp_buf b_lt;            // LTR tree: the N x N distance matrix, sums, live mask, row minima, records (sp_ltrtree.hip)
+    int lt_chunk = 0;       // starts a sketch chunk holds (0: the default) and the neighbour-joining driver (0: by size),
+    int lt_mode = 0;        // see sp_ltr_sketch_set_chunk / sp_nj_set_mode
+    int64_t lt_guard = 0;   // the guard of the joins (0: SP_LT_DMAX), see sp_nj_set_guard
     sp_buf b_wtab, b_enr;   // window table (device) and the enrichment outputs
     sp_blocks_state *blocks = nullptr;   // per-chromosome single-copy k-mer indexes of the block stage (sp_blocks.hip)
     sp_ltrdetect_state *ltrdetect = nullptr;   // chunk size, seed capacity and the last HSP list of the LTR detection (sp_ltrdetect.hip)

@@ -201,6 +201,7 @@ int sp_ctx_destroy(sp_ctx *ctx) {
     sp_buf_free(ctx->b_kb);
     sp_buf_free(ctx->b_kp);
     sp_buf_free(ctx->b_hc);
+    sp_buf_free(ctx->b_lt);
     sp_buf_free(ctx->b_win);
     if (ctx->copy_stream) {
         hipStreamSynchronize(ctx->copy_stream);

@@ -37,6 +37,7 @@ import numpy as np
 from . import REFERENCE_VERSION, __version__
 from . import blocks as blocks_mod
 from . import ltr as ltr_mod
+from . import ltrtree as ltrtree_mod
 from . import circos, seqs, stats
 from .cluster import BOOTSTRAP_ENGINES, TEST_METHODS, Cluster
 from .config import SGConfig, check_duplicates, parse_idmap
@@ -126,7 +127,8 @@ CLI = [
     ]),
     ("LTR", "subgenome-specific LTR-RTs and their insertion ages from LTR-RT coordinates (the reference's module 3 without "
             "TEsorter and the LTR trees): the stage runs when -ltr_scn or -ltr_denovo is given, unless -just_core or "
-            "-disable_ltr; every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured", [
+            "-disable_ltr; every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured; "
+            "-ltr_tree adds this build's own tree of the subgenome-specific elements (-subsample and -disable_ltrtree are used)", [
         (("-ltr_scn",), dict(type=str, metavar="FILE", default=None,
                              help="LTR-RTs in the 12-column format of the reference's tmp/LTR.scn (ltrharvest's columns plus the "
                                   "sequence id)")),
@@ -152,6 +154,19 @@ CLI = [
                                      help="chaining: largest shift of the diagonal between two extended seeds")),
         (("-ltr_chain_join",), dict(type=int, metavar="INT", default=ltr_mod.LTR_CHAIN_JOIN,
                                     help="chaining: largest distance of an extended seed from the end of its chain")),
+        (("-ltr_tree",), dict(help="build ONE tree over the subgenome-specific LTR-RTs on the GPU and write `.ltr.tree.nwk`, "
+                                   "`.ltr.tree.map` and `.ltr.tree.<figfmt>`: MinHash sketches of the elements' k-mers, Mash "
+                                   "distances, neighbour joining, midpoint rooting.  Not a protein-domain tree and not one tree per "
+                                   "Copia / Gypsy (nothing is classified); never compared with iqtree or FastTree.  Above roughly "
+                                   "25-30 %% divergence at k = 13 the distances saturate, so unrelated families are joined in no "
+                                   "meaningful order.  At most -subsample elements (0: all; 4096 at most), chosen with "
+                                   "-bootstrap_seed; elements above 65536 bases are left out; -disable_ltrtree wins.  "
+                                   "-ggtree_options, -tree_method, -tree_options, -trimal_options and -ltr_domains run nothing",
+                              **_FLAG)),
+        (("-ltr_tree_k",), dict(type=int, metavar="INT", default=ltrtree_mod.TREE_K,
+                                help="k-mer size of the tree's sketches, odd, 9..31; provisional: judged on synthetic families only")),
+        (("-ltr_tree_sketch",), dict(type=int, metavar="INT", default=ltrtree_mod.TREE_SKETCH,
+                                     help="hashes per sketch, 16..4096; provisional: judged on synthetic families only")),
     ]),
     ("Other options", None, [
         (("-p", "-ncpu"), dict(dest="ncpu", type=int, metavar="INT", default=NCPU)),
@@ -734,6 +749,14 @@ class Pipeline:
         if band < 0:
             raise ValueError("-ltr_band {} is below 0".format(band))
         scn = getattr(self, "ltr_scn", None)
+        self._ltr_tree_built = False
+        want_tree = bool(getattr(self, "ltr_tree", False))
+        if want_tree and getattr(self, "disable_ltrtree", False):
+            logger.info("-disable_ltrtree: the LTR tree of -ltr_tree is not built")
+            want_tree = False
+        if want_tree and not all(hasattr(ctx, m) for m in ("ltr_sketch", "ltr_sketch_pairs", "nj_tree")):
+            raise RuntimeError("-ltr_tree needs a context with ltr_sketch, ltr_sketch_pairs and nj_tree (libsubphaser_hip.so); there "
+                               "is no CPU engine for the tree")
         if getattr(self, "ltr_denovo", False) and not scn:
             ltrs, scn = self._ltr_detect(lay, labels, ctx, band)
         else:
@@ -834,6 +857,61 @@ class Pipeline:
             except Exception as e:     # the figures are optional
                 logger.warning("LTR insertion ages not plotted: {}".format(e))
         self._background.append((figs[0], lambda: None, done))
+        if want_tree:
+            self._ltr_tree(lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, list(cl.sg_names))
+
+    def _ltr_tree(self, lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, sg_names):
+        """-ltr_tree: `.ltr.tree.nwk`, `.ltr.tree.map` and `.ltr.tree.<figfmt>` over the elements `.ltr.insert.data` lists as
+        subgenome-specific (the reference's enrich_ltrs; without the exchanged ones under -exclude_exchanges).  The tree is this
+        build's own object (ltrtree.py): sketches, Mash distances and neighbour joining on the device."""
+        for opt in ("ggtree_options", "tree_method", "tree_options", "trimal_options", "ltr_domains"):
+            if getattr(self, opt, None):
+                logger.warning("-{} {}: no alignment or tree program is run; the tree comes from MinHash sketches and neighbour "
+                               "joining".format(opt, getattr(self, opt)))
+        k, s = int(getattr(self, "ltr_tree_k", ltrtree_mod.TREE_K)), int(getattr(self, "ltr_tree_sketch", ltrtree_mod.TREE_SKETCH))
+        limit, seed = int(getattr(self, "subsample", ltrtree_mod.SUBSAMPLE)), getattr(self, "bootstrap_seed", None)
+        if limit < 0:
+            raise ValueError("-subsample {} is below 0".format(limit))
+        exclude = bool(getattr(self, "exclude_exchanges", False))
+        picked = [i for i, r in enumerate(ltrs) if r.id in d_enriched and not (exclude and d_exchange.get(r.id) == "yes")]
+        too_long = [i for i in picked if en[i] - st[i] > ltrtree_mod.MAX_LEN]
+        if too_long:
+            logger.info("LTR tree: {} elements above {} bases are left out".format(len(too_long), ltrtree_mod.MAX_LEN))
+            picked = [i for i in picked if en[i] - st[i] <= ltrtree_mod.MAX_LEN]
+        cap = min(limit, ltrtree_mod.MAX_N) if limit else ltrtree_mod.MAX_N
+        if len(picked) > cap:
+            logger.info("LTR tree: {} of the {} subgenome-specific elements are kept (-subsample; at most {} in one tree)".format(
+                cap, len(picked), ltrtree_mod.MAX_N))
+            picked = [picked[q] for q in ltrtree_mod.choose(len(picked), cap, 0 if seed is None else seed)]
+        if len(picked) < ltrtree_mod.MIN_SEQS:
+            logger.info("LTR tree: {} subgenome-specific elements, fewer than {}: no tree".format(len(picked), ltrtree_mod.MIN_SEQS))
+            return
+        idx = np.array(picked, np.int64)
+        ids, sgs = [ltrs[i].id for i in picked], [d_enriched[ltrs[i].id] for i in picked]
+        records, (t_sk, t_pr, t_nj) = ltrtree_mod.build(ctx, chrom[idx], st[idx], en[idx], k, s)
+        logger.info("LTR tree of {} elements (k = {}, {} hashes): sketches {:.2f} s, pairs {:.2f} s, neighbour joining {:.2f} s".format(
+            len(picked), k, s, t_sk, t_pr, t_nj))
+        nwk, tmap, fig = lay.out("ltr.tree.nwk"), lay.out("ltr.tree.map"), lay.out("ltr.tree." + self.figfmt)
+        with open(nwk, "w") as fout:
+            fout.write(ltrtree_mod.tree_text(records, ids) + "\n")
+        mk_ckp(lay.ckp(nwk))
+        with open(tmap, "w") as fout:
+            ltrtree_mod.write_map(fout, ids, sgs)
+        mk_ckp(lay.ckp(tmap))
+        logger.info("LTR tree -> `{}` (midpoint-rooted; one tree, no clades: nothing is classified)".format(os.path.basename(nwk)))
+        self._ltr_tree_built = True
+        pal = getattr(self, "colors", None)
+
+        def done():      # on the main thread, with the other figures
+            try:
+                colors = pal.split(",") if isinstance(pal, str) else pal
+                sg_colors = {sg: colors[i % len(colors)] for i, sg in enumerate(sg_names)} if colors else None
+                ltrtree_mod.plot(fig, records, sgs, sg_colors)
+                if os.path.exists(fig):
+                    mk_ckp(lay.ckp(fig))
+            except Exception as e:     # the figure is optional
+                logger.warning("LTR tree not plotted: {}".format(e))
+        self._background.append((fig, lambda: None, done))
 
     def run(self):
         self._background = []
@@ -869,7 +947,13 @@ class Pipeline:
             ran_ltr = (bool(getattr(self, "ltr_scn", None)) or denovo) and not self.disable_ltr
             if ran_ltr:
                 self.stage_ltr(lay, labels, cl, kmer_labels)
-            if ran_ltr and denovo:
+            if ran_ltr and getattr(self, "_ltr_tree_built", False):
+                logger.info("Of modules 3-4, {}TEsorter classification and the circos figure are not part of this build{}; the tree "
+                            "of -ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain trees; "
+                            "run the reference on the outputs above for them".format(
+                                "" if denovo else "LTR detection, ",
+                                " (the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's)" if denovo else ""))
+            elif ran_ltr and denovo:
                 logger.info("Of modules 3-4, TEsorter classification, the LTR trees and the circos figure are not part of this build "
                             "(the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's); run the reference on "
                             "the outputs above for them")
