@@ -9,10 +9,11 @@ supplies and uses every record of it, as the reference does under -all_ltr.  Wha
 the `.ltr.insert.data` / `.ltr.insert.summary` writers; the similarity is computed from the resident genome by
 Context.ltr_align (csrc/sp_ltralign.h) unless -ltr_identity scn asks for the file's.
 
-Under -ltr_denovo the `.scn` is written here instead of read: Context.ltr_seeds / ltr_hsps give the extended exact seeds of
-a chromosome (csrc/sp_ltrdetect.h), chain_hsps joins them into chains, candidates keeps the chains that look like an
-LTR pair, similarity filters them by the alignment of the two LTRs and write_scn writes the 12 columns."""
+Under -ltr_denovo the `.scn` is written here instead of read: detect runs the loop -- Context.ltr_seeds / ltr_hsps give the
+extended exact seeds of a chromosome (csrc/sp_ltrdetect.h), chain_hsps joins them into chains, candidates keeps the chains
+that look like an LTR pair, similarity filters them by the alignment of the two LTRs -- and write_scn writes the 12 columns."""
 import math
+import time
 
 import numpy as np
 
@@ -24,6 +25,7 @@ LTR_BAND = 64
 # -mindistltr 1000 -maxdistltr 15000 -xdrop ... -similar 85), and the two of the chaining.  Provisional, as LTR_BAND is.
 LTR_SEED, LTR_MINDIST, LTR_MAXDIST, LTR_MINLEN, LTR_MAXLEN, LTR_XDROP, LTR_SIMILAR = 20, 1000, 15000, 100, 7000, 20, 85.0
 LTR_CHAIN_INDEL, LTR_CHAIN_JOIN = 32, 200
+DETECT_OPTIONS = ("seed", "mindist", "maxdist", "minlen", "maxlen", "xdrop", "similar", "chain_indel", "chain_join")   # -ltr_<name>
 IDENTITY_MODES = ("align", "scn")
 MAX_OVL = 10
 
@@ -150,6 +152,34 @@ def similarity(counts, similar=LTR_SIMILAR):
         if sims[-1] >= similar:
             keep.append(i)
     return sims, keep, dropped
+
+
+def detect(ctx, labels, band, opt):
+    """-ltr_denovo on the resident genome, opt = {name: value} of the DETECT_OPTIONS: per chromosome the extended seeds of
+    the device, chained here, and the chains that look like an LTR pair; then ONE ltr_align call for all candidates and the
+    similarity filter.  (records, tallies: what was counted on the way, and the seconds of the two parts)"""
+    if not 1 <= opt["minlen"] <= opt["maxlen"]:
+        raise ValueError("-ltr_minlen {} is below 1 or above -ltr_maxlen {}".format(opt["minlen"], opt["maxlen"]))
+    if opt["chain_indel"] < 0 or opt["chain_join"] < 0:
+        raise ValueError("-ltr_chain_indel {} or -ltr_chain_join {} is below 0".format(opt["chain_indel"], opt["chain_join"]))
+    t0 = time.perf_counter()
+    n_seeds = n_hsps = n_chains = dropped = 0
+    cands = []                     # (chromosome index, a0, a1, b0, b1)
+    for ci in range(len(labels)):
+        ns, nh = ctx.ltr_seeds(ci, opt["seed"], opt["xdrop"], opt["mindist"], opt["maxdist"], opt["maxlen"])
+        p0, ln, d = ctx.ltr_hsps(nh)
+        chains = chain_hsps(zip(p0.tolist(), ln.tolist(), d.tolist()), opt["chain_indel"], opt["chain_join"])
+        n_seeds, n_hsps, n_chains = n_seeds + ns, n_hsps + nh, n_chains + len(chains)
+        cands += [(ci,) + c for c in candidates(chains, opt["minlen"], opt["maxlen"], opt["mindist"], opt["maxdist"])]
+    t1 = time.perf_counter()
+    ltrs = []
+    if cands:
+        ci, a0, a1, b0, b1 = (np.array(x, np.int64) for x in zip(*cands))
+        counts = np.asarray(ctx.ltr_align(ci.astype(np.int32), a0, a1 - a0, b0, b1 - b0, band))
+        sims, keep, dropped = similarity(counts, opt["similar"])
+        ltrs = [Record.from_coords(labels[cands[i][0]], cands[i][0], *cands[i][1:], sims[i]) for i in keep]
+    return ltrs, dict(seeds=n_seeds, hsps=n_hsps, chains=n_chains, candidates=len(cands), dropped=dropped,
+                      t_seeds=t1 - t0, t_align=time.perf_counter() - t1)
 
 
 def resolve_overlaps(ltrs, max_ovl=MAX_OVL):

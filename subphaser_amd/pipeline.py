@@ -1,13 +1,16 @@
-"""`subphaser` command line for modules 1-2: ingest -> count -> matrix/filter -> cluster -> bin map ->
-window enrichment -> custom features -> homoeologous blocks, on the MI355X hot path.
+"""`subphaser` command line for modules 1-2 and parts of 3-4: ingest -> count -> matrix/filter -> cluster (PCA, heatmap)
+-> bin map -> window enrichment -> custom features -> homoeologous blocks -> LTR-RTs, on the MI355X hot path.
 
 What is kept from the reference is its CONTRACT: the flag surface (subphaser/__main__.py:29-248), the names
 and formats of the files under `-o` / `-tmpdir` and the checkpoint files, so that
 modules 3-4 of the reference (LTR, circos) and existing command lines keep working on these outputs.
-How the run is organised is this build's own: a `Layout` that owns every path, five stages with explicit
-inputs and outputs, and a second half that never leaves the device between the bin map, the window stack
-and the Fisher tests -- `.subgenome.bin.count` is written FROM the device arrays as an output, it is not
-parsed back (the reference re-reads it with Circos.stack_matrix before it can enrich).
+How the run is organised is this build's own: one option record (the `CLI` table's defaults under the caller's
+options: a stage reads `self.<option>`, never a default of its own), a `Layout` that owns every path, seven
+stages with explicit inputs and outputs (stage_ingest, stage_count_filter, stage_cluster, stage_windows,
+stage_features, stage_blocks, stage_ltr), one queue of writers and figures that finish on the main thread, and a
+second half that never leaves the device between the bin map, the window stack and the Fisher tests --
+`.subgenome.bin.count` is written FROM the device arrays as an output, it is not parsed back (the reference
+re-reads it with Circos.stack_matrix before it can enrich).
 
 Of modules 3-4 one step is here: the homoeologous blocks of the circos figure's innermost ring (step_blocks,
 __main__.py:699-713).  The reference runs an aligner on every pair of homoeologous chromosomes; stage_blocks votes
@@ -20,8 +23,10 @@ reference's LTR step writes), maps the subgenome-specific k-mers onto the elemen
 `.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data` / `.summary` and the two age figures; the
 divergence of an element's two LTRs comes from a banded alignment on the device (ltr.py, csrc/sp_ltralign.hip).  With
 -ltr_denovo instead of -ltr_scn the coordinates are detected on the resident genome first (csrc/sp_ltrdetect.hip: exact
-seeds, gapless extension; ltr.py: chaining) and written as `.ltr.scn`.  ltr_finder / ltrharvest themselves, TEsorter, the
-LTR trees and the circos figure itself stay with the reference.
+seeds, gapless extension; ltr.detect: the loop over the chromosomes and the chaining) and written as `.ltr.scn`.  With
+-ltr_tree the subgenome-specific elements get ONE tree of this build's own: MinHash sketches and neighbour joining on the
+device (ltrtree.py, csrc/sp_ltrtree.hip), `.ltr.tree.nwk` / `.map` and a figure.  ltr_finder / ltrharvest themselves,
+TEsorter, the reference's protein-domain trees and the circos figure itself stay with the reference.
 """
 import argparse
 import io
@@ -110,7 +115,7 @@ CLI = [
      + [((o,), dict(nargs="+", default=None)) for o in ("-ltr_detectors", "-ltr_domains", "-alt_cfgs")]
      + [((o,), _FLAG) for o in ("-disable_ltr", "-all_ltr", "-intact_ltr", "-exclude_exchanges", "-non_specific",
                                 "-disable_ltrtree", "-disable_circos", "-disable_blocks")]
-     + [(("-mu",), dict(type=float, default=13e-9)), (("-subsample",), dict(type=int, default=1000)),
+     + [(("-mu",), dict(type=float, default=13e-9)), (("-subsample",), dict(type=int, default=ltrtree_mod.SUBSAMPLE)),
         (("-window_size",), dict(type=int, metavar="INT", default=1000000)),
         (("-min_block",), dict(type=int, default=blocks_mod.MIN_BLOCK,
                                help="shortest homoeologous block (span on the first chromosome of the pair) that is kept"))]),
@@ -183,6 +188,11 @@ CLI = [
                                            "resamples the same k-mers under both)")),
     ]),
 ]
+
+
+def option_defaults():
+    """{dest: default} of every option of the `CLI` table: what the parser gives a command line that names none of them"""
+    return {kw.get("dest", flags[0].lstrip("-")): kw.get("default") for _, _, options in CLI for flags, kw in options}
 
 
 def makeArgparse(argv=None):
@@ -262,8 +272,32 @@ def _bg_min_rows():
 
 
 class Pipeline:
-    def __init__(self, genomes, sg_cfgs, labels=None, **opts):
+    # Every option is a CLASS attribute at its default of the `CLI` table (set below the class); an instance holds what its
+    # caller gave.  So an object put together by hand -- Pipeline.__new__ and some attributes -- reads the parser's defaults
+    # for the rest, too.
+    _ltr_tree_built = False      # stage_ltr wrote a tree (it starts by putting this back): _run words its closing note by it
+
+    def _configure(self, opts):
+        """the state of a run and the caller's options (the others are the class's defaults); -colors as a list or None"""
+        self._reset()
         self.__dict__.update(opts)
+        if isinstance(self.colors, str):
+            self.colors = self.colors.split(",")
+
+    def _reset(self):
+        """the containers of a run's state"""
+        self._background = []             # (name, wait, done) of the writers and figures that finish on the main thread
+        self.d_targets = {}               # ids as they are in the input -> labels (stage_ingest)
+
+    @classmethod
+    def bare(cls, **over):
+        """A pipeline with its options and nothing read: no genome, no config file.  For a single stage, and for tests."""
+        p = cls.__new__(cls)
+        p._configure(over)
+        return p
+
+    def __init__(self, genomes, sg_cfgs, labels=None, **opts):
+        self._configure(opts)
         check_duplicates(genomes)
         check_duplicates(labels)
         self.genomes, self.sg_cfgs = genomes, sg_cfgs
@@ -425,12 +459,29 @@ class Pipeline:
         if err is not None:
             raise err
 
+    def _plot_later(self, lay, what, figs, draw):
+        """Queue draw() for the MAIN thread, behind the writers (why not a writer thread: _write_matrix_in_background).
+        Each of `figs` that exists afterwards gets its checkpoint; a figure is optional: any failure is a warning."""
+        def done():
+            try:
+                draw()
+                for fig in figs:
+                    if os.path.exists(fig):
+                        mk_ckp(lay.ckp(fig))
+            except Exception as e:
+                logger.warning("{} not plotted: {}".format(what, e))
+        self._background.append((figs[0], lambda: None, done))
+
+    def _sg_colors(self, sg_names):
+        """{subgenome: colour} from -colors, in the order of the names; None without -colors: the figure's own cycle"""
+        return {sg: self.colors[i % len(self.colors)] for i, sg in enumerate(sg_names)} if self.colors else None
+
     # ---- stage 3: subgenome assignment + subgenome-specific k-mers --------------------------------------
     def stage_cluster(self, lay, d_mat2, assigned):
         logger.info("###Step: Cluster")
         cl = Cluster(d_mat2, n_clusters=self.nsg, sg_prefix="SG", sg_assigned=assigned, bootstrap=True,
                      replicates=self.replicates, jackknife=self.jackknife, seed=self.bootstrap_seed,
-                     bootstrap_engine=getattr(self, "bootstrap_engine", "sklearn"))
+                     bootstrap_engine=self.bootstrap_engine)
         logger.info("Subgenome assignments: {}".format(dict(cl.d_sg)))
         with open(lay.out("chrom-subgenome.tsv"), "w") as fout:
             cl.output_subgenomes(fout)
@@ -460,7 +511,7 @@ class Pipeline:
         tsv, fig = lay.out("kmer_pca.tsv"), lay.out("kmer_pca." + self.figfmt)
         t0 = time.perf_counter()
         try:
-            draw = cl.pca(outfig=fig, outtsv=tsv, n_components=self.nsg or cl.n_clusters, colors=getattr(self, "colors", None),
+            draw = cl.pca(outfig=fig, outtsv=tsv, n_components=self.nsg or cl.n_clusters, colors=self.colors,
                           defer=True)
         except Exception as e:
             if isinstance(e, ValueError) and str(e).startswith("Input contains NaN or infinity"):
@@ -469,37 +520,27 @@ class Pipeline:
             return
         mk_ckp(lay.ckp(tsv))
         logger.info("k-mer PCA ({}) -> `{}` in {:.2f} s".format(cl.pca_engine, os.path.basename(tsv), time.perf_counter() - t0))
-
-        def done():
-            try:
-                draw()
-                if os.path.exists(fig):
-                    mk_ckp(lay.ckp(fig))
-            except Exception as e:     # the figure is optional
-                logger.warning("k-mer PCA not plotted: {}".format(e))
-        self._background.append((fig, lambda: None, done))
+        self._plot_later(lay, "k-mer PCA", [fig], draw)
 
     def _heatmap(self, lay, cl, kmer_labels):
         """`.kmer.mat.heatmap.tsv` and `.kmer.mat.<figfmt>` (the reference's figure name, __main__.py:461-464).  The table
         is written here, the figure with the background writers (drawn on the main thread, as the PCA's).  Only a wrong
         number of -heatmap_colors stops the run, as it stops the reference; any other failure costs these two files."""
-        size = getattr(self, "heatmap_size", 10000)
-        if getattr(self, "heatmap_options", ""):
+        if self.heatmap_options:
             logger.warning("-heatmap_options is R syntax for heatmap.2; the heatmap is drawn without R and ignores `{}`".format(
                 self.heatmap_options))
-        if size is None or size <= 0:
-            logger.info("heatmap skipped: -heatmap_size {}".format(size))
+        if self.heatmap_size is None or self.heatmap_size <= 0:
+            logger.info("heatmap skipped: -heatmap_size {}".format(self.heatmap_size))
             return
         if len(cl.chrs) < 2:
             logger.info("heatmap skipped: {} chromosome".format(len(cl.chrs)))
             return
         from .heatmap import check_colors
-        panel = check_colors(getattr(self, "heatmap_colors", ("green", "black", "red")))      # ValueError: stops the run
-        matfile = lay.out("kmer.mat")
-        tsv, fig = matfile + ".heatmap.tsv", matfile + "." + self.figfmt
+        panel = check_colors(self.heatmap_colors)      # ValueError: stops the run
+        tsv, fig = lay.out("kmer.mat.heatmap.tsv"), lay.out("kmer.mat." + self.figfmt)
         t0 = time.perf_counter()
         try:
-            draw = cl.heatmap(kmer_labels, outfig=fig, outtsv=tsv, size=size, colors=getattr(self, "colors", None),
+            draw = cl.heatmap(kmer_labels, outfig=fig, outtsv=tsv, size=self.heatmap_size, colors=self.colors,
                               heatmap_colors=panel, defer=True)
         except Exception as e:
             logger.warning("heatmap not written: {}".format(e))
@@ -508,15 +549,7 @@ class Pipeline:
             return
         mk_ckp(lay.ckp(tsv))
         logger.info("heatmap ({}) -> `{}` in {:.2f} s".format(cl.heatmap_engine, os.path.basename(tsv), time.perf_counter() - t0))
-
-        def done():
-            try:
-                draw()
-                if os.path.exists(fig):
-                    mk_ckp(lay.ckp(fig))
-            except Exception as e:     # the figure is optional
-                logger.warning("heatmap not plotted: {}".format(e))
-        self._background.append((fig, lambda: None, done))
+        self._plot_later(lay, "heatmap", [fig], draw)
 
     # ---- stage 4: bin map -> window stack -> enrichment, on the device -----------------------------------
     def stage_windows(self, lay, chromfiles, labels, d_size, cl, kmer_labels):
@@ -567,16 +600,11 @@ class Pipeline:
             if beds:
                 # intervals: a reduction over the genome the GPU already holds; ids are synthesised as chrom:start-end
                 # (what enrich_ltr's id rule expects); BED names may be the ids before or after renaming
+                sub = io.StringIO() if fastas else fout      # behind FASTA lines: without a second header line
+                seqs.map_intervals(beds, kmer_labels, {lab: i for i, lab in enumerate(self.labels)}, fout=sub, k=self.k,
+                                   bin_size=FEATURE_BIN, sg_names=cl.sg_names, collect=ivals, aliases=dict(self.d_targets))
                 if fastas:
-                    sub = io.StringIO()
-                    seqs.map_intervals(beds, kmer_labels, {lab: i for i, lab in enumerate(self.labels)}, fout=sub, k=self.k,
-                                       bin_size=FEATURE_BIN, sg_names=cl.sg_names, collect=ivals,
-                                       aliases=dict(getattr(self, "d_targets", None) or {}))
                     fout.write(sub.getvalue().split("\n", 1)[1])      # one header line per file
-                else:
-                    seqs.map_intervals(beds, kmer_labels, {lab: i for i, lab in enumerate(self.labels)}, fout=fout, k=self.k,
-                                       bin_size=FEATURE_BIN, sg_names=cl.sg_names, collect=ivals,
-                                       aliases=dict(getattr(self, "d_targets", None) or {}))
         logger.info("feature enrichment")
         S = len(cl.sg_names)
         ids, counts = [], []
@@ -600,16 +628,10 @@ class Pipeline:
                     # lines that share an id are ONE row whatever file they came from (Circos.stack_matrix,
                     # Circos.py:709-742, sums them): a BED interval listed twice, or listed next to a FASTA record of
                     # the same id, must give the row the intervals-only branch above gives (advisor r04)
-                    where, m_ids, m_counts = {}, [], []
+                    merged = {}      # id -> summed row, in the order of the ids' first lines
                     for rid, row in zip(ids, counts):
-                        j = where.get(rid)
-                        if j is None:
-                            where[rid] = len(m_ids)
-                            m_ids.append(rid)
-                            m_counts.append(list(row))
-                        else:
-                            m_counts[j] = [x + y for x, y in zip(m_counts[j], row)]
-                    ids, counts = m_ids, m_counts
+                        merged[rid] = [x + y for x, y in zip(merged[rid], row)] if rid in merged else list(row)
+                    ids, counts = list(merged), list(merged.values())
                 enriched, _ = stats.enrich_ltr(fout, cl.d_sg, np.asarray(counts, np.int64).reshape(len(ids), S),
                                                colnames=cl.sg_names, rownames=ids, max_pval=self.max_pval)
         logger.info("wrote {}".format(feat_enrich))
@@ -622,7 +644,7 @@ class Pipeline:
         """`blocks.tsv`, `block_link.txt` and `blocks.<figfmt>` from the anchor vote of every homoeologous pair (the pair
         list of Blocks.run_align over the config lines, or over -alt_cfgs).  A failure costs these files and nothing else."""
         for opt in ("aligner", "aligner_options"):
-            if getattr(self, opt, None):
+            if getattr(self, opt):
                 logger.warning("-{} {}: no aligner is run; blocks come from shared single-copy k-mers".format(opt, getattr(self, opt)))
         if int(os.environ.get("WORLD_SIZE", "1")) > 1:
             logger.info("blocks skipped: the stage runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
@@ -633,8 +655,8 @@ class Pipeline:
             return
         try:
             sgs = self.sgs
-            if getattr(self, "alt_cfgs", None):      # another grouping for this stage only (__main__.py:280-286)
-                rename = (getattr(self, "d_targets", None) or {}).get
+            if self.alt_cfgs:      # another grouping for this stage only (__main__.py:280-286)
+                rename = self.d_targets.get
                 sgs = [[[rename(c, c) for c in unit] for unit in line]
                        for f in self.alt_cfgs for line in SGConfig(f, sep=self.sep).sgs]
             known = set(labels)
@@ -674,60 +696,61 @@ class Pipeline:
             except Exception:
                 pass
             return
-        d_sg, sg_names, pal = dict(getattr(cl, "d_sg", None) or {}), list(getattr(cl, "sg_names", None) or []), getattr(self, "colors", None)
+        d_sg, sg_names = dict(getattr(cl, "d_sg", None) or {}), list(getattr(cl, "sg_names", None) or [])
 
-        def done():      # on the main thread, with the other figures (see _write_matrix_in_background)
-            try:
-                from matplotlib import pyplot as plt
-                colors = pal.split(",") if isinstance(pal, str) else (pal or plt.rcParams["axes.prop_cycle"].by_key()["color"])
-                chrom_colors = {c: colors[sg_names.index(sg) % len(colors)] for c, sg in d_sg.items() if sg in sg_names}
-                blocks_mod.plot(fig, res, dict(zip(labels, lengths)), chrom_colors)
-                if os.path.exists(fig):
-                    mk_ckp(lay.ckp(fig))
-            except Exception as e:     # the figure is optional
-                logger.warning("blocks not plotted: {}".format(e))
-        self._background.append((fig, lambda: None, done))
+        def draw():
+            from matplotlib import pyplot as plt
+            colors = self.colors or plt.rcParams["axes.prop_cycle"].by_key()["color"]
+            chrom_colors = {c: colors[sg_names.index(sg) % len(colors)] for c, sg in d_sg.items() if sg in sg_names}
+            blocks_mod.plot(fig, res, dict(zip(labels, lengths)), chrom_colors)
+        self._plot_later(lay, "blocks", [fig], draw)
 
     # ---- stage 7: LTR-RTs from a .scn, or detected -----------------------------------------------------------
-    def _ltr_detect(self, lay, labels, ctx, band):
-        """-ltr_denovo: the LTR-RT candidates of every chromosome, written to `.ltr.scn` -- per chromosome the extended seeds
-        of the device (Context.ltr_seeds / ltr_hsps) chained on the host, then one ltr_align call for all candidates and the
-        similarity filter (ltr.py).  There is no CPU detector: a context without ltr_seeds is an error."""
+    def stage_ltr(self, lay, labels, cl, kmer_labels):
+        """`.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data`, `.ltr.insert.summary` and the two age
+        figures from the LTR-RTs of -ltr_scn (step_ltr, __main__.py:549-620, without detection and classification), or from
+        those -ltr_denovo detects and writes to `.ltr.scn`; with -ltr_tree the tree of the subgenome-specific ones."""
+        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+            logger.info("LTR stage skipped: it runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
+            return
+        logger.info("###Step: LTR")
+        ctx = get_context()
+        band = int(self.ltr_band)
+        if band < 0:
+            raise ValueError("-ltr_band {} is below 0".format(band))
+        self._ltr_tree_built = False
+        want_tree = self.ltr_tree
+        if want_tree and self.disable_ltrtree:
+            logger.info("-disable_ltrtree: the LTR tree of -ltr_tree is not built")
+            want_tree = False
+        if want_tree and not all(hasattr(ctx, m) for m in ("ltr_sketch", "ltr_sketch_pairs", "nj_tree")):      # before anything is written
+            raise RuntimeError("-ltr_tree needs a context with ltr_sketch, ltr_sketch_pairs and nj_tree (libsubphaser_hip.so); there "
+                               "is no CPU engine for the tree")
+        ltrs, chrom, st, en = self._ltr_records(lay, labels, ctx, band)
+        d_enriched, d_exchange = self._ltr_enrich(lay, ctx, cl, kmer_labels, ltrs, chrom, st, en)
+        ages = self._ltr_ages(lay, ctx, ltrs, chrom, band)
+        if not d_enriched:
+            logger.warning("Because of none subgenome-specific LTR-RTs, plots of LTR-RTs are skipped.")
+            return
+        if self._ltr_insert(lay, ltrs, ages, d_enriched, d_exchange, list(cl.sg_names)) and want_tree:
+            self._ltr_tree(lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, list(cl.sg_names))
+
+    def _ltr_detected(self, lay, labels, ctx, band):
+        """-ltr_denovo: (records, path) of the LTR-RTs ltr.detect finds, written to `.ltr.scn`; there is no CPU detector"""
         if not (hasattr(ctx, "ltr_seeds") and hasattr(ctx, "ltr_hsps") and hasattr(ctx, "ltr_align")):
             raise RuntimeError("-ltr_denovo needs a context with ltr_seeds, ltr_hsps and ltr_align (libsubphaser_hip.so); there is "
                                "no CPU detector: pass -ltr_scn FILE instead")
-        opt = {name: getattr(self, "ltr_" + name, default) for name, default in (
-            ("seed", ltr_mod.LTR_SEED), ("mindist", ltr_mod.LTR_MINDIST), ("maxdist", ltr_mod.LTR_MAXDIST), ("minlen", ltr_mod.LTR_MINLEN),
-            ("maxlen", ltr_mod.LTR_MAXLEN), ("xdrop", ltr_mod.LTR_XDROP), ("similar", ltr_mod.LTR_SIMILAR),
-            ("chain_indel", ltr_mod.LTR_CHAIN_INDEL), ("chain_join", ltr_mod.LTR_CHAIN_JOIN))}
-        if not 1 <= opt["minlen"] <= opt["maxlen"]:
-            raise ValueError("-ltr_minlen {} is below 1 or above -ltr_maxlen {}".format(opt["minlen"], opt["maxlen"]))
-        if opt["chain_indel"] < 0 or opt["chain_join"] < 0:
-            raise ValueError("-ltr_chain_indel {} or -ltr_chain_join {} is below 0".format(opt["chain_indel"], opt["chain_join"]))
+        opt = {name: getattr(self, "ltr_" + name) for name in ltr_mod.DETECT_OPTIONS}
         logger.info("Detecting LTR-RTs: seed {seed}, distance {mindist}-{maxdist}, LTR length {minlen}-{maxlen}, X-drop {xdrop}, "
                     "similarity >= {similar}, chaining {chain_indel} / {chain_join}; no TSD or motif search".format(**opt))
-        t0 = time.perf_counter()
-        n_seeds = n_hsps = n_chains = 0
-        cands = []                     # (chromosome index, a0, a1, b0, b1)
-        for ci in range(len(labels)):
-            ns, nh = ctx.ltr_seeds(ci, opt["seed"], opt["xdrop"], opt["mindist"], opt["maxdist"], opt["maxlen"])
-            p0, ln, d = ctx.ltr_hsps(nh)
-            chains = ltr_mod.chain_hsps(zip(p0.tolist(), ln.tolist(), d.tolist()), opt["chain_indel"], opt["chain_join"])
-            n_seeds, n_hsps, n_chains = n_seeds + ns, n_hsps + nh, n_chains + len(chains)
-            cands += [(ci,) + c for c in ltr_mod.candidates(chains, opt["minlen"], opt["maxlen"], opt["mindist"], opt["maxdist"])]
+        ltrs, n = ltr_mod.detect(ctx, labels, band, opt)
         logger.info("{} seeds, {} extended seeds (HSPs), {} chains, {} candidates on {} chromosomes in {:.2f} s".format(
-            n_seeds, n_hsps, n_chains, len(cands), len(labels), time.perf_counter() - t0))
-        ltrs = []
-        if cands:
-            t0 = time.perf_counter()
-            ci, a0, a1, b0, b1 = (np.array(x, np.int64) for x in zip(*cands))
-            counts = np.asarray(ctx.ltr_align(ci.astype(np.int32), a0, a1 - a0, b0, b1 - b0, band))
-            sims, keep, dropped = ltr_mod.similarity(counts, opt["similar"])
-            if dropped:
-                logger.info("{} candidates outside the limits of the alignment (band {}) or without an aligned column: dropped".format(dropped, band))
-            ltrs = [ltr_mod.Record.from_coords(labels[cands[i][0]], cands[i][0], *cands[i][1:], sims[i]) for i in keep]
+            n["seeds"], n["hsps"], n["chains"], n["candidates"], len(labels), n["t_seeds"]))
+        if n["dropped"]:
+            logger.info("{} candidates outside the limits of the alignment (band {}) or without an aligned column: dropped".format(n["dropped"], band))
+        if n["candidates"]:
             logger.info("{} candidates aligned (band {}) in {:.2f} s; {} with similarity >= {}".format(
-                len(cands), band, time.perf_counter() - t0, len(ltrs), opt["similar"]))
+                n["candidates"], band, n["t_align"], len(ltrs), opt["similar"]))
         scn = lay.out("ltr.scn")
         with open(scn, "w") as fout:
             ltr_mod.write_scn(fout, ltrs)
@@ -735,37 +758,18 @@ class Pipeline:
         logger.info("{} LTR-RTs detected, written to `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
         return ltrs, scn
 
-    def stage_ltr(self, lay, labels, cl, kmer_labels):
-        """`.ltr.bin.count`, `.ltr.enrich`, `.ltr.identity.tsv`, `.ltr.insert.data`, `.ltr.insert.summary` and the two age
-        figures from the LTR-RTs of -ltr_scn (step_ltr, __main__.py:549-620, without detection and classification), or from
-        those -ltr_denovo detects and writes to `.ltr.scn`."""
-        if int(os.environ.get("WORLD_SIZE", "1")) > 1:
-            logger.info("LTR stage skipped: it runs on one GPU, this is a run of {} ranks".format(os.environ["WORLD_SIZE"]))
-            return
-        logger.info("###Step: LTR")
-        ctx = get_context()
-        mode = getattr(self, "ltr_identity", "align")
-        band = int(getattr(self, "ltr_band", ltr_mod.LTR_BAND))
-        if band < 0:
-            raise ValueError("-ltr_band {} is below 0".format(band))
-        scn = getattr(self, "ltr_scn", None)
-        self._ltr_tree_built = False
-        want_tree = bool(getattr(self, "ltr_tree", False))
-        if want_tree and getattr(self, "disable_ltrtree", False):
-            logger.info("-disable_ltrtree: the LTR tree of -ltr_tree is not built")
-            want_tree = False
-        if want_tree and not all(hasattr(ctx, m) for m in ("ltr_sketch", "ltr_sketch_pairs", "nj_tree")):
-            raise RuntimeError("-ltr_tree needs a context with ltr_sketch, ltr_sketch_pairs and nj_tree (libsubphaser_hip.so); there "
-                               "is no CPU engine for the tree")
-        if getattr(self, "ltr_denovo", False) and not scn:
-            ltrs, scn = self._ltr_detect(lay, labels, ctx, band)
+    def _ltr_records(self, lay, labels, ctx, band):
+        """The elements the stage works on: read or detected, on target chromosomes, inside them, overlaps resolved, with their
+        (chromosome index, start, end): the reference's seq[start:end], the Python slice taken with the 1-based start."""
+        if self.ltr_denovo and not self.ltr_scn:
+            ltrs, scn = self._ltr_detected(lay, labels, ctx, band)
         else:
-            ltrs = ltr_mod.read_scn(scn)
+            ltrs, scn = ltr_mod.read_scn(self.ltr_scn), self.ltr_scn
             logger.info("{} LTRs read from `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
-        aliases, index = dict(getattr(self, "d_targets", None) or {}), {lab: i for i, lab in enumerate(labels)}
+        index = {lab: i for i, lab in enumerate(labels)}
         known = []
         for r in ltrs:
-            r.seq_id = aliases.get(r.seq_id, r.seq_id)
+            r.seq_id = self.d_targets.get(r.seq_id, r.seq_id)
             if r.seq_id in index:
                 known.append(r)
         if len(known) < len(ltrs):
@@ -775,21 +779,23 @@ class Pipeline:
             if not (1 <= r.start and r.lltr >= 1 and r.rltr >= 1 and r.lltr_e <= r.end and r.start <= r.rltr_s and r.end <= lengths[index[r.seq_id]]):
                 raise ValueError("{}: LTR-RT {} does not lie on its chromosome (length {}) or its LTRs (lengths {}, {}) do not lie in it".format(
                     scn, r.id, lengths[index[r.seq_id]], r.lltr, r.rltr))
-        n_known = len(known)
         ltrs = ltr_mod.group_resolve_overlaps(known)
-        logger.info("After filtering, {} / {} ({:.1%}) LTRs retained".format(len(ltrs), n_known, len(ltrs) / max(1, n_known)))
-        # map: the element is the reference's seq[start:end] -- the Python slice taken with the 1-based start
-        S, names = len(cl.sg_names), list(cl.sg_names)
+        logger.info("After filtering, {} / {} ({:.1%}) LTRs retained".format(len(ltrs), len(known), len(ltrs) / max(1, len(known))))
         chrom = np.array([index[r.seq_id] for r in ltrs], np.int32)
         st, en = np.array([r.start for r in ltrs], np.int64), np.array([r.end for r in ltrs], np.int64)
         if len(ltrs) and int((en - st).max()) > FEATURE_BIN:
             raise ValueError("{}: an LTR-RT of {} bases is longer than a {}-base bin".format(scn, int((en - st).max()), FEATURE_BIN))
+        return ltrs, chrom, st, en
+
+    def _ltr_enrich(self, lay, ctx, cl, kmer_labels, ltrs, chrom, st, en):
+        """`.ltr.bin.count` (mapped elements only) and `.ltr.enrich`: ({id: subgenome} enriched, {id: "yes" / "no"} exchanged)"""
+        S, names = len(cl.sg_names), list(cl.sg_names)
         ctx.labels_set(kmer_labels.keys, kmer_labels.sg_idx, S)
         counts = np.asarray(ctx.map_intervals(chrom, st, en), np.int64).reshape(len(ltrs), S) if len(ltrs) else np.zeros((0, S), np.int64)
         hit = np.flatnonzero(counts.sum(axis=1) > 0).tolist()
         ltr_map = lay.out("ltr.bin.count")
         logger.info("Outputing `coordinate` - `LTR` maps to `{}`".format(ltr_map))
-        with open(ltr_map, "w") as fout:      # only mapped LTRs are output
+        with open(ltr_map, "w") as fout:
             fout.write("\t".join(["#chrom", "start", "end"] + names) + "\n")
             for i in hit:
                 fout.write("{}\t0\t{}\t{}\n".format(ltrs[i].id, int(en[i] - st[i]), "\t".join(map(str, counts[i].tolist()))))
@@ -807,8 +813,11 @@ class Pipeline:
         logger.info("{} significant subgenome-specific LTR-RTs".format(len(d_enriched)))
         for sg, n in sorted(Counter(d_enriched.values()).items()):
             logger.info("\t{} {}-specific LTR-RTs".format(n, sg))
-        # identity and ages
-        aligned = None
+        return d_enriched, d_exchange
+
+    def _ltr_ages(self, lay, ctx, ltrs, chrom, band):
+        """`.ltr.identity.tsv`: the divergence of every element's two LTRs under -ltr_identity and its age at -mu; the ages"""
+        mode, aligned = self.ltr_identity, None
         if not hasattr(ctx, "ltr_align"):
             if mode == "align":
                 logger.info("this context has no ltr_align: -ltr_identity scn is used")
@@ -828,9 +837,10 @@ class Pipeline:
         with open(ident, "w") as fout:
             ltr_mod.write_identity(fout, ltrs, aligned, divs, ages)
         mk_ckp(lay.ckp(ident))
-        if not d_enriched:
-            logger.warning("Because of none subgenome-specific LTR-RTs, plots of LTR-RTs are skipped.")
-            return
+        return ages
+
+    def _ltr_insert(self, lay, ltrs, ages, d_enriched, d_exchange, sg_names):
+        """`.ltr.insert.data`, `.ltr.insert.summary` and the two age figures; False: -exclude_exchanges left nothing to date"""
         prefix = lay.out("ltr.insert")
         with open(prefix + ".data", "w") as fout:
             d_data, _, excluded = ltr_mod.write_insert_data(fout, ltrs, ages, d_enriched, d_exchange,
@@ -839,41 +849,26 @@ class Pipeline:
             logger.info("{} potentially exchanged LTR-RTs are excluded".format(excluded))
         if not d_data:      # every enriched element was excluded as an exchange
             logger.warning("no LTR-RT is left to date: `{}` and the plots are skipped".format(os.path.basename(prefix + ".summary")))
-            return
+            return False
         with open(prefix + ".summary", "w") as fout:
             d_info = ltr_mod.summary_ltr_time(d_data, fout)
         mk_ckp(lay.ckp(prefix + ".summary"))
         figs = [prefix + ".density." + self.figfmt, prefix + ".histo." + self.figfmt]
-        sg_names, pal = list(cl.sg_names), getattr(self, "colors", None)
-
-        def done():      # on the main thread, with the other figures (see _write_matrix_in_background)
-            try:
-                colors = pal.split(",") if isinstance(pal, str) else pal
-                sg_colors = {sg: colors[i % len(colors)] for i, sg in enumerate(sg_names)} if colors else None
-                ltr_mod.plot(d_data, d_info, figs[0], figs[1], sg_colors)
-                for fig in figs:
-                    if os.path.exists(fig):
-                        mk_ckp(lay.ckp(fig))
-            except Exception as e:     # the figures are optional
-                logger.warning("LTR insertion ages not plotted: {}".format(e))
-        self._background.append((figs[0], lambda: None, done))
-        if want_tree:
-            self._ltr_tree(lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, list(cl.sg_names))
+        self._plot_later(lay, "LTR insertion ages", figs, lambda: ltr_mod.plot(d_data, d_info, figs[0], figs[1], self._sg_colors(sg_names)))
+        return True
 
     def _ltr_tree(self, lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, sg_names):
         """-ltr_tree: `.ltr.tree.nwk`, `.ltr.tree.map` and `.ltr.tree.<figfmt>` over the elements `.ltr.insert.data` lists as
         subgenome-specific (the reference's enrich_ltrs; without the exchanged ones under -exclude_exchanges).  The tree is this
         build's own object (ltrtree.py): sketches, Mash distances and neighbour joining on the device."""
         for opt in ("ggtree_options", "tree_method", "tree_options", "trimal_options", "ltr_domains"):
-            if getattr(self, opt, None):
+            if getattr(self, opt):
                 logger.warning("-{} {}: no alignment or tree program is run; the tree comes from MinHash sketches and neighbour "
                                "joining".format(opt, getattr(self, opt)))
-        k, s = int(getattr(self, "ltr_tree_k", ltrtree_mod.TREE_K)), int(getattr(self, "ltr_tree_sketch", ltrtree_mod.TREE_SKETCH))
-        limit, seed = int(getattr(self, "subsample", ltrtree_mod.SUBSAMPLE)), getattr(self, "bootstrap_seed", None)
+        k, s, limit, seed = int(self.ltr_tree_k), int(self.ltr_tree_sketch), int(self.subsample), self.bootstrap_seed
         if limit < 0:
             raise ValueError("-subsample {} is below 0".format(limit))
-        exclude = bool(getattr(self, "exclude_exchanges", False))
-        picked = [i for i, r in enumerate(ltrs) if r.id in d_enriched and not (exclude and d_exchange.get(r.id) == "yes")]
+        picked = [i for i, r in enumerate(ltrs) if r.id in d_enriched and not (self.exclude_exchanges and d_exchange.get(r.id) == "yes")]
         too_long = [i for i in picked if en[i] - st[i] > ltrtree_mod.MAX_LEN]
         if too_long:
             logger.info("LTR tree: {} elements above {} bases are left out".format(len(too_long), ltrtree_mod.MAX_LEN))
@@ -900,21 +895,10 @@ class Pipeline:
         mk_ckp(lay.ckp(tmap))
         logger.info("LTR tree -> `{}` (midpoint-rooted; one tree, no clades: nothing is classified)".format(os.path.basename(nwk)))
         self._ltr_tree_built = True
-        pal = getattr(self, "colors", None)
-
-        def done():      # on the main thread, with the other figures
-            try:
-                colors = pal.split(",") if isinstance(pal, str) else pal
-                sg_colors = {sg: colors[i % len(colors)] for i, sg in enumerate(sg_names)} if colors else None
-                ltrtree_mod.plot(fig, records, sgs, sg_colors)
-                if os.path.exists(fig):
-                    mk_ckp(lay.ckp(fig))
-            except Exception as e:     # the figure is optional
-                logger.warning("LTR tree not plotted: {}".format(e))
-        self._background.append((fig, lambda: None, done))
+        self._plot_later(lay, "LTR tree", [fig], lambda: ltrtree_mod.plot(fig, records, sgs, self._sg_colors(sg_names)))
 
     def run(self):
-        self._background = []
+        self._reset()
         try:
             self._run()
         except BaseException:
@@ -943,26 +927,25 @@ class Pipeline:
                 self.stage_features(lay, cl, kmer_labels)
             if not (self.disable_circos or self.disable_blocks):
                 self.stage_blocks(lay, labels, d_size, cl)
-            denovo = bool(getattr(self, "ltr_denovo", False)) and not getattr(self, "ltr_scn", None)
-            ran_ltr = (bool(getattr(self, "ltr_scn", None)) or denovo) and not self.disable_ltr
-            if ran_ltr:
+            denovo = self.ltr_denovo and not self.ltr_scn
+            if (self.ltr_scn or denovo) and not self.disable_ltr:
                 self.stage_ltr(lay, labels, cl, kmer_labels)
-            if ran_ltr and getattr(self, "_ltr_tree_built", False):
-                logger.info("Of modules 3-4, {}TEsorter classification and the circos figure are not part of this build{}; the tree "
-                            "of -ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain trees; "
-                            "run the reference on the outputs above for them".format(
-                                "" if denovo else "LTR detection, ",
-                                " (the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's)" if denovo else ""))
-            elif ran_ltr and denovo:
-                logger.info("Of modules 3-4, TEsorter classification, the LTR trees and the circos figure are not part of this build "
-                            "(the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's); run the reference on "
-                            "the outputs above for them")
-            elif ran_ltr:
-                logger.info("Of modules 3-4, LTR detection, TEsorter classification, the LTR trees and the circos figure are not "
-                            "part of this build; run the reference on the outputs above for them")
+                # the closing note: what of modules 3-4 this run did not do itself
+                missing = ([] if denovo else ["LTR detection"]) + ["TEsorter classification"] + ([] if self._ltr_tree_built else ["the LTR trees"])
+                logger.info("Of modules 3-4, {} and the circos figure are not part of this build{}{}; run the reference on the outputs above "
+                            "for them".format(
+                                ", ".join(missing),
+                                " (the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's)" if denovo else "",
+                                "; the tree of -ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain "
+                                "trees" if self._ltr_tree_built else ""))
             elif not (self.disable_ltr and self.disable_circos):
                 logger.info("Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
                             "outputs above, or pass -disable_ltr -disable_circos to silence this note")
+
+
+for _dest, _default in option_defaults().items():
+    setattr(Pipeline, _dest, _default)
+
 
 def main(argv=None):
     args = makeArgparse(argv)

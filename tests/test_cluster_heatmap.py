@@ -229,12 +229,9 @@ class _Lay:
 
 def _pipeline(**kw):
     from subphaser_amd import pipeline
-    p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-    p.__dict__.update(nsg=3, replicates=0, jackknife=50, bootstrap_seed=1, max_pval=0.05, test_method="ttest_ind",
-                      figfmt="png", colors=None, heatmap_size=SIZE, heatmap_colors=("green", "black", "red"),
-                      heatmap_options="", _background=[])
-    p.__dict__.update(kw)
-    return p
+    opts = dict(nsg=3, replicates=0, bootstrap_seed=1, figfmt="png", heatmap_size=SIZE)
+    opts.update(kw)
+    return pipeline.Pipeline.bare(**opts)
 
 
 def test_option_is_parsed():

@@ -192,10 +192,7 @@ class _StagingTwin(kp.TwinContext):
 
 def _pipeline(nsg=3):
     from subphaser_amd import pipeline
-    p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-    p.__dict__.update(nsg=nsg, replicates=0, jackknife=50, bootstrap_seed=1, max_pval=0.05, test_method="ttest_ind",
-                      figfmt="png", colors=None, _background=[])
-    return p
+    return pipeline.Pipeline.bare(nsg=nsg, replicates=0, bootstrap_seed=1, figfmt="png")
 
 
 def test_stage_cluster_runs_pca_before_the_rows_are_released(tmp_path, caplog):

@@ -129,11 +129,9 @@ LABELS = ["c0", "c1", "c2", "lone"]
 
 
 def _pipe(tmp_path, sgs, **over):
-    p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-    opts = dict(sgs=sgs, sep="|", alt_cfgs=None, aligner=None, aligner_options=None, block_k=21, block_sample=1, block_bin=500,
-                block_votes=3, block_gap=5, min_block=1500, figfmt="png", colors=None, d_targets={}, _background=[])
+    opts = dict(sgs=sgs, block_k=21, block_sample=1, block_bin=500, block_votes=3, block_gap=5, min_block=1500, figfmt="png")
     opts.update(over)
-    p.__dict__.update(opts)
+    p = pipeline.Pipeline.bare(**opts)
     seqs = list(bc.trio()) + ["ACGT" * 50]
     stub = _Stub(seqs)
     return p, stub, _Lay(tmp_path), {lab: len(s) for lab, s in zip(LABELS, seqs)}
@@ -207,11 +205,9 @@ def test_alt_cfgs_replace_the_lines_for_this_stage(tmp_path, with_ctx):
 def test_switches_that_skip_the_stage(monkeypatch):
     """-just_core, -disable_circos and -disable_blocks: the reference's conditions; the stage follows the feature stage"""
     def run(**flags):
-        p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-        opts = dict(outdir="o", tmpdir="t", prefix=None, k=15, min_freq=200, min_fold=2, just_core=False, disable_circos=False,
-                    disable_blocks=False, disable_ltr=True, custom_features=["f.bed"], _background=[])
+        opts = dict(outdir="o", tmpdir="t", disable_ltr=True, custom_features=["f.bed"])
         opts.update(flags)
-        p.__dict__.update(opts)
+        p = pipeline.Pipeline.bare(**opts)
         order = []
 
         class _Cl:
@@ -276,6 +272,26 @@ def test_a_failure_costs_the_files_and_nothing_else(tmp_path, with_ctx, caplog):
     assert warn == ["blocks not written: sp_blocks_index: an index of 1 bytes does not fit on the device"]
     assert sorted(os.listdir(tmp_path)) == ["run.bin.enrich"] and earlier.read_text() == "kept\n"
     assert stub.calls[-1] == ("release", -1) and not p._background
+
+
+def test_a_figure_that_fails_is_a_warning(tmp_path, with_ctx, caplog, monkeypatch):
+    p, stub, lay, d_size = _pipe(tmp_path, [[["c0"], ["c1"]]])
+
+    def boom(*a):
+        raise OSError("no room for the figure")
+    monkeypatch.setattr(bl, "plot", boom)
+    with_ctx(stub)
+    with caplog.at_level(logging.INFO, logger="subphaser_amd"):
+        p.stage_blocks(lay, LABELS, d_size)
+        p._finish_background()                       # does not raise: the run goes on
+    warn = [r.getMessage() for r in caplog.records if r.levelno >= logging.WARNING]
+    assert len(warn) == 1 and warn[0].startswith("blocks not plotted: ") and not p._background
+    try:
+        import matplotlib  # noqa: F401
+        assert warn == ["blocks not plotted: no room for the figure"]
+    except ImportError:
+        pass
+    assert os.path.exists(lay.ckp(lay.out("blocks.tsv"))) and not os.path.exists(lay.ckp(lay.out("blocks.png")))
 
 
 def test_cli_options():

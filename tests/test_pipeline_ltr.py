@@ -77,11 +77,9 @@ def with_ctx():
 def _pipe(tmp_path, gold, scn_text=None, **over):
     scn = tmp_path / "LTR.scn"
     scn.write_text(gold["scn"] if scn_text is None else scn_text)
-    p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-    opts = dict(ltr_scn=str(scn), ltr_identity="align", ltr_band=64, d_targets={}, max_pval=0.05, mu=gold["mu"], exclude_exchanges=False,
-                non_specific=False, figfmt="png", colors=None, _background=[])
+    opts = dict(ltr_scn=str(scn), mu=gold["mu"], figfmt="png")
     opts.update(over)
-    p.__dict__.update(opts)
+    p = pipeline.Pipeline.bare(**opts)
     out = tmp_path / "out"
     out.mkdir(exist_ok=True)
     return p, _Lay(out)
@@ -271,11 +269,9 @@ def test_errors_and_skips(tmp_path, world, caplog, with_ctx, monkeypatch):
 def test_switches_that_skip_the_stage(monkeypatch, caplog):
     """the stage follows the feature and block stages; it needs -ltr_scn and runs unless -just_core or -disable_ltr"""
     def run(**flags):
-        p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-        opts = dict(outdir="o", tmpdir="t", prefix=None, k=15, min_freq=200, min_fold=2, just_core=False, disable_circos=False,
-                    disable_blocks=False, disable_ltr=False, custom_features=["f.bed"], ltr_scn="x.scn", _background=[])
+        opts = dict(outdir="o", tmpdir="t", custom_features=["f.bed"], ltr_scn="x.scn")
         opts.update(flags)
-        p.__dict__.update(opts)
+        p = pipeline.Pipeline.bare(**opts)
         order = []
 
         class _C:

@@ -100,12 +100,9 @@ def with_ctx():
 
 
 def _pipe(root, **over):
-    p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-    opts = dict(ltr_scn=None, ltr_denovo=True, ltr_identity="align", ltr_band=64, d_targets={}, max_pval=0.05, mu=13e-9, exclude_exchanges=False,
-                non_specific=False, figfmt="png", colors=None, _background=[])
+    opts = dict(ltr_denovo=True, figfmt="png")
     opts.update(over)
-    p.__dict__.update(opts)
-    return p, _Lay(root)
+    return pipeline.Pipeline.bare(**opts), _Lay(root)
 
 
 def _run(p, lay, world, ctx, caplog, with_ctx):
@@ -210,11 +207,9 @@ def test_no_cpu_detector_and_ranks(tmp_path, world, caplog, with_ctx, monkeypatc
 
 def test_switches(monkeypatch, caplog):
     def run(**flags):
-        p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-        opts = dict(outdir="o", tmpdir="t", prefix=None, k=15, min_freq=200, min_fold=2, just_core=False, disable_circos=True,
-                    disable_blocks=False, disable_ltr=False, custom_features=None, ltr_scn=None, ltr_denovo=False, _background=[])
+        opts = dict(outdir="o", tmpdir="t", disable_circos=True)
         opts.update(flags)
-        p.__dict__.update(opts)
+        p = pipeline.Pipeline.bare(**opts)
         order = []
 
         class _C:

@@ -125,11 +125,9 @@ def test_flag_off_changes_nothing(tmp_path, world, caplog, with_ctx):
 
 def test_closing_note(monkeypatch, caplog):
     def run(built, **flags):
-        p = pipeline.Pipeline.__new__(pipeline.Pipeline)
-        opts = dict(outdir="o", tmpdir="t", prefix=None, k=15, min_freq=200, min_fold=2, just_core=False, disable_circos=True,
-                    disable_blocks=True, disable_ltr=False, custom_features=None, ltr_scn=None, ltr_denovo=False, _background=[])
+        opts = dict(outdir="o", tmpdir="t", disable_circos=True, disable_blocks=True)
         opts.update(flags)
-        p.__dict__.update(opts)
+        p = pipeline.Pipeline.bare(**opts)
 
         class _C:
             d_sg, sg_names = {}, []
@@ -143,14 +141,16 @@ def test_closing_note(monkeypatch, caplog):
         with caplog.at_level(logging.INFO, logger="subphaser_amd"):
             p._run()
         return [r.getMessage() for r in caplog.records]
-    log = run(True, ltr_denovo=True, ltr_tree=True)
-    assert len(log) == 1 and log[0].startswith("Of modules 3-4, TEsorter classification and the circos figure are not part of this build "
-                                               "(the LTR-RTs are this build's own detection")
-    assert "the LTR trees" not in log[0] and "not the reference's domain trees" in log[0]
-    log = run(True, ltr_scn="x.scn", ltr_tree=True)
-    assert log[0].startswith("Of modules 3-4, LTR detection, TEsorter classification and the circos figure are not part of this build;")
-    assert "the LTR trees" not in log[0]
-    # no tree built (flag off, disabled, or fewer than 4 elements): the texts of today, byte for byte
+    # the five texts, byte for byte
+    assert run(True, ltr_denovo=True, ltr_tree=True) == [
+        "Of modules 3-4, TEsorter classification and the circos figure are not part of this build "
+        "(the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's); the tree of -ltr_tree is this build's own "
+        "(sketches and neighbour joining), not the reference's domain trees; run the reference on the outputs above for them"]
+    assert run(True, ltr_scn="x.scn", ltr_tree=True) == [
+        "Of modules 3-4, LTR detection, TEsorter classification and the circos figure are not part of this build; the tree of "
+        "-ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain trees; run the reference on the "
+        "outputs above for them"]
+    # no tree built (flag off, disabled, or fewer than 4 elements)
     assert run(False, ltr_denovo=True, ltr_tree=True) == [
         "Of modules 3-4, TEsorter classification, the LTR trees and the circos figure are not part of this build "
         "(the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's); run the reference on "
@@ -158,6 +158,25 @@ def test_closing_note(monkeypatch, caplog):
     assert run(False, ltr_scn="x.scn") == [
         "Of modules 3-4, LTR detection, TEsorter classification, the LTR trees and the circos figure are not "
         "part of this build; run the reference on the outputs above for them"]
+    # no LTR stage: neither -ltr_scn nor -ltr_denovo, or -disable_ltr; nothing once -disable_circos is given too
+    for flags in (dict(), dict(disable_circos=False, disable_ltr=True, ltr_scn="x.scn")):
+        assert run(False, **flags) == [
+            "Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
+            "outputs above, or pass -disable_ltr -disable_circos to silence this note"]
+    assert run(False, disable_ltr=True, ltr_denovo=True) == []
+
+
+def test_option_record_is_the_parsers():
+    """every option has ONE default, the `CLI` table's: a pipeline built without the parser reads what the parser would give"""
+    args = vars(pipeline.makeArgparse(["-i", "g.fa", "-c", "sg.config"]))      # no -pre: outdir and tmpdir are not rewritten
+    record = pipeline.option_defaults()
+    assert set(record) == set(args)
+    p = pipeline.Pipeline.bare()
+    for dest in sorted(set(args) - {"genomes", "sg_cfgs"}):
+        assert record[dest] == args[dest] and type(record[dest]) is type(args[dest]), dest
+        assert getattr(p, dest) == args[dest] and getattr(pipeline.Pipeline, dest) == args[dest], dest      # the class's, not a copy
+    assert (p._background, p.d_targets, p._ltr_tree_built) == ([], {}, False)
+    assert pipeline.Pipeline.bare(colors="red,#00ff00").colors == ["red", "#00ff00"] and p.colors is None
 
 
 def test_cli_options():
