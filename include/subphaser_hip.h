@@ -481,6 +481,28 @@ int sp_nj_tree(sp_ctx *ctx, const int64_t *dist, int N, int64_t *merges);
 int sp_nj_set_mode(sp_ctx *ctx, int mode);
 int sp_nj_set_guard(sp_ctx *ctx, int64_t limit);
 
+/* ---- LTR-RT classification: profile-HMM domains in the six-frame translation of the inner sequences ------
+ * The search is defined by integer arithmetic (csrc/sp_domains.h holds the definition: frames, genetic code, the pair
+ * order, the recurrence, the hit and its tie order, the ranges); it is this build's own local Viterbi search, one hit per
+ * (frame, profile), and is not hmmscan.  The step from a HMMER3 text file to the tables is host arithmetic
+ * (subphaser_amd/domains.py: read_hmm).
+ *   sp_dom_search   n intervals [start[i], end[i]) (0-based, half-open; empty is fine and means no hit) of chromosome
+ *                   chrom[i] on the genome of sp_genome_add against P profiles.  Profile p has M_p = moff[p + 1] - moff[p]
+ *                   nodes (moff[0] = 0); its match emissions are rows moff[p] .. of `emis` (22 columns: the residues A C D E
+ *                   F G H I K L M N P Q R S T V W Y, a codon with an invalid base, a stop codon), its transitions rows
+ *                   moff[p] .. of `trans` (7 columns: m->m, m->i, m->d, i->m, i->i, d->m, d->d), its local entry entry[p];
+ *                   units of 1/256 bit.  The tables go up once per call.  out: n x P x 6 int32, caller-owned host memory,
+ *                   per (element, profile) = score, frame (0..2 forward, 3..5 reverse complement), i_start, i_end (residues
+ *                   of the frame, 0-based, inclusive), k_start, k_end (nodes, 1-based, inclusive); no residue in any
+ *                   frame: INT32_MIN and zeros.  One wave per (element, frame, profile), longest first.  n = 0 is fine.
+ * SP_EINVAL: a NULL pointer; no genome; a chromosome out of range; an interval off its chromosome or with end < start;
+ * P < 1; offsets that do not ascend from 0 (an M < 1); a transition or entry outside [-2^20, 0] or an emission outside
+ * [-2^20, 2^15] -- all checked on the host before any launch.  SP_EUNSUP: M > 2048, an interval above 65536 bases,
+ * P > 4096, n x P > 2^24 -- decided before any allocation.  SP_ENOMEM: the workspace does not fit (the message has its
+ * size).                                                                                                                  */
+int sp_dom_search(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int P,
+                  const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry, int32_t *out);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

@@ -25,6 +25,10 @@ BLOCKS_K_RANGE, BLOCKS_MAX_SAMPLE = (17, 31), 16   # SP_BK_KMIN, SP_BK_KMAX (odd
 LTR_ALIGN_MAXLEN, LTR_ALIGN_MAXBAND = 8192, 1024    # SP_LA_MAXLEN, SP_LA_MAXBAND in csrc/sp_ltralign.h
 LTR_ALIGN_EDGE, LTR_ALIGN_BAND, LTR_ALIGN_LEN = 1, 2, 4   # SP_LA_F_*: the flag bits of ltr_align's last column
 LTRTREE_MAX_LEN, LTRTREE_MAX_N = 65536, 4096       # SP_LT_MAXLEN, SP_LT_MAXN in csrc/sp_ltrtree.h
+DOMAINS_MAX_M, DOMAINS_MAX_LEN, DOMAINS_MAX_P = 2048, 65536, 4096   # SP_DM_MAXM, SP_DM_MAXLEN, SP_DM_MAXP in csrc/sp_domains.h
+DOMAINS_MAX_ENTRIES = 1 << 24                      # (element, profile) entries of one sp_dom_search call
+DOMAINS_CALL_ENTRIES = 1 << 20                     # entries Context.dom_search puts in one call: the library lists and sorts six
+                                                   # items of 24 bytes per entry on the host, 150 MB at this size (2.4 GB at the limit)
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
@@ -38,6 +42,7 @@ SYMBOLS = [
     "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
     "sp_ltr_align", "sp_ltr_seeds", "sp_ltr_hsps", "sp_ltr_detect_set_chunk", "sp_ltr_detect_set_capacity",
     "sp_ltr_sketch", "sp_ltr_sketch_set_chunk", "sp_ltr_sketch_pairs", "sp_nj_tree", "sp_nj_set_mode", "sp_nj_set_guard",
+    "sp_dom_search",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -145,6 +150,7 @@ def load():
     L.sp_ltr_detect_set_capacity.argtypes = [vp, i64]
     L.sp_ltr_sketch.argtypes = [vp, i64, vp, vp, vp, ci, ci, vp, vp]
     L.sp_ltr_sketch_set_chunk.argtypes = [vp, ci]
+    L.sp_dom_search.argtypes = [vp, i64, vp, vp, vp, ci, vp, vp, vp, vp, vp]
     L.sp_ltr_sketch_pairs.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.sp_nj_tree.argtypes = [vp, vp, ci, vp]
     L.sp_nj_set_mode.argtypes = [vp, ci]
@@ -1041,6 +1047,32 @@ class Context:
         shared, denom = np.empty((n, n), np.int32), np.empty((n, n), np.int32)
         self._ck(self.L.sp_ltr_sketch_pairs(self.h, int(n), int(s), _p(sketch), _p(length), _p(shared), _p(denom)))
         return shared, denom
+
+    # -------------------------------------------------------------- LTR domains
+    def dom_search(self, chrom, start, end, moff, emis, trans, entry):
+        """Local Viterbi search of P profile HMMs in the six-frame translation of the intervals [start, end) (0-based,
+        half-open; an empty one has no hit) on the resident genome (sp_dom_search; definition in csrc/sp_domains.h):
+        int32 [n, P, 6] = score (1/256 bit), frame, i_start, i_end, k_start, k_end; INT32_MIN and zeros where no frame has
+        a residue.  moff int32 [P + 1], emis int32 [sum M, 22], trans int32 [sum M, 7], entry int32 [P] (domains.read_hmm
+        makes them).  The elements go in calls of at most DOMAINS_CALL_ENTRIES (element, profile) entries -- far below the
+        library's limit DOMAINS_MAX_ENTRIES, so that the host lists of a call stay small; a profile set above that alone
+        goes an element at a time."""
+        chrom = np.ascontiguousarray(chrom, np.int32)
+        start, end = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+        moff, entry = np.ascontiguousarray(moff, np.int32), np.ascontiguousarray(entry, np.int32)
+        emis, trans = np.ascontiguousarray(emis, np.int32), np.ascontiguousarray(trans, np.int32)
+        n, P = int(chrom.size), int(moff.size) - 1
+        if start.size != n or end.size != n:
+            raise ValueError("chrom, start and end must have one entry per element")
+        if P >= 1 and (entry.size != P or emis.size != int(moff[-1]) * 22 or trans.size != int(moff[-1]) * 7):
+            raise ValueError("the tables must have entry [P], emis [sum M, 22] and trans [sum M, 7] for moff [P + 1]")
+        out = np.empty((n, max(P, 0), 6), np.int32)
+        step = max(1, DOMAINS_CALL_ENTRIES // max(P, 1))
+        for a in range(0, max(n, 1), step):
+            b = min(n, a + step)
+            self._ck(self.L.sp_dom_search(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans),
+                                          _p(entry), _p(out[a:b])))
+        return out
 
     def nj_tree(self, dist):
         """Neighbour joining on a symmetric int64 [N, N] matrix with zero diagonal and entries in [0, 2^31)

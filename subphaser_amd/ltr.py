@@ -182,19 +182,25 @@ def detect(ctx, labels, band, opt):
                       t_seeds=t1 - t0, t_align=time.perf_counter() - t1)
 
 
-def resolve_overlaps(ltrs, max_ovl=MAX_OVL):
-    """resolve_overlaps (LTR.py:422-468) for records of one sequence none of which is "completed": walking by start, of two
-    records that overlap by more than max_ovl % of the shorter the longer stays (the earlier on a tie) and is what the next
-    record is compared with; of two equal records the later goes.  What is returned is set(ltrs) - set(discards) with the
-    reference's equality -- the key (seq_id, start, end, lltr_e, rltr_s) -- so a discarded record takes every record of its
-    key with it.  Order: (start, end, lltr_e, rltr_s) (the reference leaves equal starts in set order)."""
+def resolve_overlaps(ltrs, max_ovl=MAX_OVL, completed=None):
+    """resolve_overlaps (LTR.py:422-468) for records of one sequence: walking by start, of two records that overlap by more
+    than max_ovl % of the shorter the longer stays (the earlier on a tie) and is what the next record is compared with; of
+    two equal records the later goes.  `completed`: the keys of the records a classification calls complete (None: none is,
+    as without -ltr_hmm) -- when exactly one of the two is complete, it stays whatever the lengths.  What is returned is
+    set(ltrs) - set(discards) with the reference's equality -- the key (seq_id, start, end, lltr_e, rltr_s) -- so a
+    discarded record takes every record of its key with it.  Order: (start, end, lltr_e, rltr_s) (the reference leaves
+    equal starts in set order)."""
+    done = completed or ()
     last, discards = None, set()
     for ltr in sorted(ltrs, key=lambda x: x.start):
         if last is not None:
             if ltr.key == last.key:
                 discard = ltr
             elif ltr.overlap(last) > max_ovl:
-                discard = last if ltr.element_len > last.element_len else ltr
+                if (ltr.key in done) != (last.key in done):
+                    discard = last if ltr.key in done else ltr
+                else:
+                    discard = last if ltr.element_len > last.element_len else ltr
             else:
                 last = ltr
                 continue
@@ -210,14 +216,14 @@ def resolve_overlaps(ltrs, max_ovl=MAX_OVL):
     return sorted(kept, key=lambda x: (x.start, x.end, x.lltr_e, x.rltr_s))
 
 
-def group_resolve_overlaps(ltrs):
+def group_resolve_overlaps(ltrs, completed=None):
     """group_resolve_overlaps (LTR.py:415-420): runs of consecutive records of one sequence, each resolved on its own"""
     out, i = [], 0
     while i < len(ltrs):
         j = i
         while j < len(ltrs) and ltrs[j].seq_id == ltrs[i].seq_id:
             j += 1
-        out += resolve_overlaps(ltrs[i:j])
+        out += resolve_overlaps(ltrs[i:j], completed=completed)
         i = j
     return out
 

@@ -245,11 +245,12 @@ def build(ctx, chrom, start, end, k, s):
     return records, (t1 - t0, t2 - t1, time.perf_counter() - t3)
 
 
-def write_map(fout, labels, sgs):
-    """`.ltr.tree.map`: the reference's columns label, Clade, Subgenome; there is no classification, so Clade is `unknown`"""
+def write_map(fout, labels, sgs, clades=None):
+    """`.ltr.tree.map`: the reference's columns label, Clade, Subgenome; Clade is `unknown` unless the elements were classified
+    (-ltr_hmm: `clades`, one per label)"""
     fout.write("\t".join(["label", "Clade", "Subgenome"]) + "\n")
-    for lab, sg in zip(labels, sgs):
-        fout.write("\t".join([str(lab), "unknown", str(sg)]) + "\n")
+    for q, (lab, sg) in enumerate(zip(labels, sgs)):
+        fout.write("\t".join([str(lab), "unknown" if clades is None else str(clades[q]), str(sg)]) + "\n")
 
 
 def plot(path, records, sgs, sg_colors=None):

@@ -25,7 +25,9 @@ divergence of an element's two LTRs comes from a banded alignment on the device 
 -ltr_denovo instead of -ltr_scn the coordinates are detected on the resident genome first (csrc/sp_ltrdetect.hip: exact
 seeds, gapless extension; ltr.detect: the loop over the chromosomes and the chaining) and written as `.ltr.scn`.  With
 -ltr_tree the subgenome-specific elements get ONE tree of this build's own: MinHash sketches and neighbour joining on the
-device (ltrtree.py, csrc/sp_ltrtree.hip), `.ltr.tree.nwk` / `.map` and a figure.  ltr_finder / ltrharvest themselves,
+device (ltrtree.py, csrc/sp_ltrtree.hip), `.ltr.tree.nwk` / `.map` and a figure.  With -ltr_hmm the records are classified
+from the protein domains of their inner sequences first (domains.py, csrc/sp_domains.hip: this build's own Viterbi search of the
+user's profile HMMs, TEsorter's rules behind it): `.ltr.dom.gff3`, `.ltr.cls.tsv`, records that are no LTR-RTs dropped.  ltr_finder / ltrharvest themselves,
 TEsorter, the reference's protein-domain trees and the circos figure itself stay with the reference.
 """
 import argparse
@@ -41,6 +43,7 @@ import numpy as np
 
 from . import REFERENCE_VERSION, __version__
 from . import blocks as blocks_mod
+from . import domains as domains_mod
 from . import ltr as ltr_mod
 from . import ltrtree as ltrtree_mod
 from . import circos, seqs, stats
@@ -131,9 +134,10 @@ CLI = [
                                help="windows a block may skip, and drift off its diagonal, between two called windows")),
     ]),
     ("LTR", "subgenome-specific LTR-RTs and their insertion ages from LTR-RT coordinates (the reference's module 3 without "
-            "TEsorter and the LTR trees): the stage runs when -ltr_scn or -ltr_denovo is given, unless -just_core or "
-            "-disable_ltr; every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured; "
-            "-ltr_tree adds this build's own tree of the subgenome-specific elements (-subsample and -disable_ltrtree are used)", [
+            "TEsorter itself and the LTR trees): the stage runs when -ltr_scn or -ltr_denovo is given, unless -just_core or "
+            "-disable_ltr; without -ltr_hmm every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured; "
+            "-ltr_tree adds this build's own tree of the subgenome-specific elements (-subsample and -disable_ltrtree are used); "
+            "-ltr_hmm classifies the records from protein domains and drops those that are no LTR-RTs (-all_ltr keeps them)", [
         (("-ltr_scn",), dict(type=str, metavar="FILE", default=None,
                              help="LTR-RTs in the 12-column format of the reference's tmp/LTR.scn (ltrharvest's columns plus the "
                                   "sequence id)")),
@@ -159,6 +163,18 @@ CLI = [
                                      help="chaining: largest shift of the diagonal between two extended seeds")),
         (("-ltr_chain_join",), dict(type=int, metavar="INT", default=ltr_mod.LTR_CHAIN_JOIN,
                                     help="chaining: largest distance of an extended seed from the end of its chain")),
+        (("-ltr_hmm",), dict(type=str, metavar="FILE", default=None,
+                             help="classify the LTR-RTs from the protein domains of their inner sequences: profile HMMs in HMMER3 "
+                                  "text format (REXdb's `.hmm` as TEsorter ships it, or any other) are searched in the six-frame "
+                                  "translation on the GPU, and TEsorter's rules give order, superfamily and clade: "
+                                  "`.ltr.dom.gff3`, `.ltr.cls.tsv`; records whose order is not LTR are dropped unless -all_ltr.  "
+                                  "The search is this build's own integer Viterbi alignment, one hit per frame and profile, "
+                                  "not hmmscan: no E-values")),
+        (("-ltr_dom_cov",), dict(type=float, metavar="FLOAT", default=domains_mod.MIN_COV,
+                                 help="minimum share of a profile's nodes a domain covers, in percent (TEsorter's 20)")),
+        (("-ltr_dom_score",), dict(type=float, metavar="FLOAT", default=domains_mod.MIN_SCORE,
+                                   help="minimum score of a domain in bits per node (TEsorter's 0.5); provisional: these bits are "
+                                        "not HMMER's")),
         (("-ltr_tree",), dict(help="build ONE tree over the subgenome-specific LTR-RTs on the GPU and write `.ltr.tree.nwk`, "
                                    "`.ltr.tree.map` and `.ltr.tree.<figfmt>`: MinHash sketches of the elements' k-mers, Mash "
                                    "distances, neighbour joining, midpoint rooting.  Not a protein-domain tree and not one tree per "
@@ -726,6 +742,23 @@ class Pipeline:
         if want_tree and not all(hasattr(ctx, m) for m in ("ltr_sketch", "ltr_sketch_pairs", "nj_tree")):      # before anything is written
             raise RuntimeError("-ltr_tree needs a context with ltr_sketch, ltr_sketch_pairs and nj_tree (libsubphaser_hip.so); there "
                                "is no CPU engine for the tree")
+        self._ltr_profiles, self._ltr_clades = None, {}
+        if self.ltr_hmm:
+            if not hasattr(ctx, "dom_search"):      # before anything is written
+                raise RuntimeError("-ltr_hmm needs a context with dom_search (libsubphaser_hip.so); there is no CPU engine for the "
+                                   "domain search")
+            self._ltr_profiles = domains_mod.read_hmm(self.ltr_hmm)
+            if len(self._ltr_profiles) > domains_mod.MAX_P or max(self._ltr_profiles.M) > domains_mod.MAX_M:
+                raise ValueError("{}: {} profiles of up to {} nodes; the domain search takes up to {} profiles of up to {} nodes".format(
+                    self.ltr_hmm, len(self._ltr_profiles), max(self._ltr_profiles.M), domains_mod.MAX_P, domains_mod.MAX_M))
+            logger.info("{} profiles of {}-{} nodes read from `{}`".format(len(self._ltr_profiles), min(self._ltr_profiles.M),
+                                                                           max(self._ltr_profiles.M), self.ltr_hmm))
+            if self.tesorter_options:
+                logger.warning("-tesorter_options {}: TEsorter is not run; the domains come from this build's own search (-ltr_hmm, "
+                               "-ltr_dom_cov, -ltr_dom_score)".format(self.tesorter_options))
+            if self.intact_ltr:
+                logger.info("-intact_ltr changes nothing, as in the reference: it is passed as intact_ltr= to a constructor whose "
+                            "parameter is intact, and is lost")
         ltrs, chrom, st, en = self._ltr_records(lay, labels, ctx, band)
         d_enriched, d_exchange = self._ltr_enrich(lay, ctx, cl, kmer_labels, ltrs, chrom, st, en)
         ages = self._ltr_ages(lay, ctx, ltrs, chrom, band)
@@ -755,8 +788,56 @@ class Pipeline:
         with open(scn, "w") as fout:
             ltr_mod.write_scn(fout, ltrs)
         mk_ckp(lay.ckp(scn))
-        logger.info("{} LTR-RTs detected, written to `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
+        logger.info("{} LTR-RTs detected, written to `{}`{}".format(len(ltrs), scn, self._ltr_unclassified_note()))
         return ltrs, scn
+
+    _ltr_profiles, _ltr_clades = None, {}      # the profiles of -ltr_hmm and {id: clade} of the classified records (stage_ltr sets them)
+
+    def _ltr_unclassified_note(self):
+        return "" if self._ltr_profiles is not None else "; no classification: every record is used, as under -all_ltr"
+
+    def _ltr_classify(self, lay, ctx, known, index):
+        """-ltr_hmm: `.ltr.dom.gff3` and `.ltr.cls.tsv` of the records (LTRpipeline.classfify and the filter of LTRpipeline.run,
+        LTR.py:335-361): the inner sequences, cut as get_int_seq cuts them, are searched on the device (Context.dom_search),
+        domains.py turns the hits into domains and classes.  Returns (the records that stay, the keys of the complete ones)."""
+        profiles, t0 = self._ltr_profiles, time.perf_counter()
+        ival = [domains_mod.inner_interval(r) for r in known]
+        long_ = [q for q, (a, b) in enumerate(ival) if b - a > domains_mod.MAX_LEN]
+        if long_:
+            logger.info("{} LTR-RTs with an inner sequence above {} bases are left unclassified".format(len(long_), domains_mod.MAX_LEN))
+        pick = [q for q, (a, b) in enumerate(ival) if b - a <= domains_mod.MAX_LEN]
+        hits = np.asarray(ctx.dom_search(np.array([index[known[q].seq_id] for q in pick], np.int32), np.array([ival[q][0] for q in pick], np.int64),
+                                         np.array([ival[q][1] for q in pick], np.int64), *profiles.tables())) if pick else np.zeros((0, len(profiles), 6), np.int32)
+        doms = domains_mod.best_domains([known[q].id for q in pick], [ival[q][1] - ival[q][0] for q in pick], hits, profiles,
+                                        float(self.ltr_dom_cov), float(self.ltr_dom_score))
+        rows = domains_mod.classify(doms)
+        gff, cls = lay.out("ltr.dom.gff3"), lay.out("ltr.cls.tsv")
+        with open(gff, "w") as fout:
+            domains_mod.write_gff(fout, doms)
+        mk_ckp(lay.ckp(gff))
+        with open(cls, "w") as fout:
+            domains_mod.write_cls(fout, rows)
+        mk_ckp(lay.ckp(cls))
+        logger.info("{} inner sequences x {} profiles searched in {:.2f} s: {} domains (coverage >= {}, score >= {} bits per node) in {} "
+                    "elements -> `{}`, `{}`".format(len(pick), len(profiles), time.perf_counter() - t0, len(doms), self.ltr_dom_cov,
+                                                    self.ltr_dom_score, len(rows), os.path.basename(gff), os.path.basename(cls)))
+        d_class = {r[0]: r for r in rows}
+        kept, completed, n_ltr, n_intact = [], set(), 0, 0
+        for r in known:
+            row = d_class.get(domains_mod.format_gff_id(r.id))
+            order, complete = (row[1], row[4]) if row else (None, None)
+            n_ltr += order == "LTR"
+            n_intact += complete == "yes"
+            if not self.all_ltr and order != "LTR":
+                continue
+            kept.append(r)
+            if row:
+                self._ltr_clades[r.id] = row[3]
+            if complete == "yes":
+                completed.add(r.key)
+        logger.info("By the device domain search, {} ({:.1%}) are classified as LTRs, of which {} ({:.1%}) are intact with complete protein "
+                    "domains".format(n_ltr, n_ltr / max(1, len(known)), n_intact, n_intact / max(1, n_ltr)))
+        return kept, completed
 
     def _ltr_records(self, lay, labels, ctx, band):
         """The elements the stage works on: read or detected, on target chromosomes, inside them, overlaps resolved, with their
@@ -765,7 +846,7 @@ class Pipeline:
             ltrs, scn = self._ltr_detected(lay, labels, ctx, band)
         else:
             ltrs, scn = ltr_mod.read_scn(self.ltr_scn), self.ltr_scn
-            logger.info("{} LTRs read from `{}`; no classification: every record is used, as under -all_ltr".format(len(ltrs), scn))
+            logger.info("{} LTRs read from `{}`{}".format(len(ltrs), scn, self._ltr_unclassified_note()))
         index = {lab: i for i, lab in enumerate(labels)}
         known = []
         for r in ltrs:
@@ -779,7 +860,10 @@ class Pipeline:
             if not (1 <= r.start and r.lltr >= 1 and r.rltr >= 1 and r.lltr_e <= r.end and r.start <= r.rltr_s and r.end <= lengths[index[r.seq_id]]):
                 raise ValueError("{}: LTR-RT {} does not lie on its chromosome (length {}) or its LTRs (lengths {}, {}) do not lie in it".format(
                     scn, r.id, lengths[index[r.seq_id]], r.lltr, r.rltr))
-        ltrs = ltr_mod.group_resolve_overlaps(known)
+        kept, completed = known, None
+        if self._ltr_profiles is not None:      # as LTRpipeline.run: classified before a record is dropped for overlap
+            kept, completed = self._ltr_classify(lay, ctx, known, index)
+        ltrs = ltr_mod.group_resolve_overlaps(kept, completed)
         logger.info("After filtering, {} / {} ({:.1%}) LTRs retained".format(len(ltrs), len(known), len(ltrs) / max(1, len(known))))
         chrom = np.array([index[r.seq_id] for r in ltrs], np.int32)
         st, en = np.array([r.start for r in ltrs], np.int64), np.array([r.end for r in ltrs], np.int64)
@@ -891,9 +975,10 @@ class Pipeline:
             fout.write(ltrtree_mod.tree_text(records, ids) + "\n")
         mk_ckp(lay.ckp(nwk))
         with open(tmap, "w") as fout:
-            ltrtree_mod.write_map(fout, ids, sgs)
+            ltrtree_mod.write_map(fout, ids, sgs, [self._ltr_clades.get(i, "unknown") for i in ids] if self._ltr_profiles is not None else None)
         mk_ckp(lay.ckp(tmap))
-        logger.info("LTR tree -> `{}` (midpoint-rooted; one tree, no clades: nothing is classified)".format(os.path.basename(nwk)))
+        logger.info("LTR tree -> `{}` (midpoint-rooted; one tree{})".format(
+            os.path.basename(nwk), ", no clades: nothing is classified" if self._ltr_profiles is None else "; the Clade column is the domain classification's"))
         self._ltr_tree_built = True
         self._plot_later(lay, "LTR tree", [fig], lambda: ltrtree_mod.plot(fig, records, sgs, self._sg_colors(sg_names)))
 
@@ -931,13 +1016,16 @@ class Pipeline:
             if (self.ltr_scn or denovo) and not self.disable_ltr:
                 self.stage_ltr(lay, labels, cl, kmer_labels)
                 # the closing note: what of modules 3-4 this run did not do itself
-                missing = ([] if denovo else ["LTR detection"]) + ["TEsorter classification"] + ([] if self._ltr_tree_built else ["the LTR trees"])
-                logger.info("Of modules 3-4, {} and the circos figure are not part of this build{}{}; run the reference on the outputs above "
-                            "for them".format(
-                                ", ".join(missing),
+                missing = (([] if denovo else ["LTR detection"]) + ([] if self.ltr_hmm else ["TEsorter classification"])
+                           + ([] if self._ltr_tree_built else ["the LTR trees"]))
+                logger.info("Of modules 3-4, {}the circos figure {} not part of this build{}{}{}; run the reference on the outputs above "
+                            "for {}".format(
+                                ", ".join(missing) + " and " if missing else "", "are" if missing else "is",
+                                "; the classification is this build's own Viterbi domain search (-ltr_hmm), not TEsorter's hmmscan"
+                                if self.ltr_hmm else "",
                                 " (the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's)" if denovo else "",
                                 "; the tree of -ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain "
-                                "trees" if self._ltr_tree_built else ""))
+                                "trees" if self._ltr_tree_built else "", "them" if missing else "it"))
             elif not (self.disable_ltr and self.disable_circos):
                 logger.info("Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
                             "outputs above, or pass -disable_ltr -disable_circos to silence this note")

@@ -1,0 +1,43 @@
+// Host check of subphaser_amd/csrc/sp_domains.h (tests/test_domains_host.py builds and runs it).
+// Input file: records, each led by an int64 tag, until tag 0:
+//   1  element: int64 n, M, then n base codes (bytes: 0..3, anything else invalid), M x 22 int32 emissions, M x 7 int32
+//      transitions, int32 entry                                                   -> 6 int32 (sp_dm_result), int32 tables_ok
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include "sp_domains.h"
+
+template <typename T>
+static bool get(FILE *f, T *out, size_t n = 1) { return n == 0 || fread(out, sizeof(T), n, f) == n; }
+template <typename T>
+static bool put(FILE *f, const T *in, size_t n = 1) { return n == 0 || fwrite(in, sizeof(T), n, f) == n; }
+
+int main(int argc, char **argv) {
+    if (argc < 3) return 2;
+    FILE *f = fopen(argv[1], "rb"), *o = fopen(argv[2], "wb");
+    if (!f || !o) return 2;
+    long checks = 0;
+    for (;;) {
+        int64_t tag = 0;
+        if (!get(f, &tag)) return 3;
+        if (tag == 0) break;
+        if (tag != 1) return 4;
+        int64_t n, M;
+        if (!get(f, &n) || !get(f, &M)) return 3;
+        if (n < 0 || n > SP_DM_MAXLEN || M < 1 || M > SP_DM_MAXM) return 4;
+        std::vector<uint8_t> codes((size_t)n), res((size_t)(n / 3 + 1));
+        std::vector<int32_t> emis((size_t)M * SP_DM_COLS), trans((size_t)M * 7);
+        std::vector<int64_t> row((size_t)(6 * (M + 1)));
+        int32_t entry, out[7];
+        if (!get(f, codes.data(), codes.size()) || !get(f, emis.data(), emis.size()) || !get(f, trans.data(), trans.size()) || !get(f, &entry)) return 3;
+        sp_dm_host_element(codes.data(), n, (int)M, emis.data(), trans.data(), entry, res.data(), row.data(), out);
+        out[6] = sp_dm_tables_ok((int)M, emis.data(), trans.data(), entry) ? 1 : 0;
+        if (!put(o, out, 7)) return 5;
+        checks++;
+    }
+    fclose(f);
+    if (fclose(o) != 0) return 5;
+    printf("OK %ld\n", checks);
+    return 0;
+}
