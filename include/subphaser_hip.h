@@ -182,7 +182,15 @@ int sp_map_bins(sp_ctx *ctx, int chrom, int64_t bin_size, int64_t chunk_size, in
  * One launch per chromosome back to back, one device->host copy.               */
 int sp_map_bins_all(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, const int64_t *slot_off,
                     int32_t *slot_counts, int64_t *n_mapped);
-/* window stack of the slot counts left on the device by the last sp_map_bins_all
+/* The three stack entries below read the table the last sp_map_bins_all left on the device.  The context
+ * remembers what that table is: bin_size, chunk_size, slot_off (all C + 1 offsets), n_sg, k and the chromosome
+ * count.  A stack entry whose bin_size, chunk_size or slot_off differ from those, or that is called after the
+ * context's n_sg, k or chromosome count moved, returns SP_EINVAL with a message naming the mismatch, before
+ * anything is launched.  The table stops being valid ("call sp_map_bins_all first") with the next sp_map_bins,
+ * sp_labels_set / sp_labels_set_device, sp_genome_reset, sp_genome_add / sp_genome_add_device, sp_count /
+ * sp_count_range.  (A sp_map_bins_all that is refused for its arguments leaves the previous table as it was.)
+ *
+ * window stack of the slot counts left on the device by the last sp_map_bins_all
  * (replaces Circos.stack_matrix, Circos.py:734-742, 831-842, without the text round trip):
  * window = (bin start) / window_size; chromosome c owns windows [win_off[c], win_off[c+1]),
  * at least len/window_size + 2 each; win_counts: total x n_sg int64 (overwritten).          */

@@ -223,13 +223,23 @@ struct sp_ctx {
     sp_buf b_fq;      // global slow queue of the filter
     sp_buf b_fflat;   // flat set tables of the filter (sp_filter.hip)
     sp_buf b_map, b_mapdesc, b_ival, b_emit, b_fpar, b_win;  // reusable device buffers of sp_map_bins / k3_emit / sp_filter / stack
-    bool map_all_valid = false;
+    // What sp_map_bins_all left in b_map, for the stack entries: they refuse any other description of it.  Ended
+    // (sp_map_table_drop) by whatever re-uses b_map or changes what its rows and columns mean: sp_map_bins, sp_labels_set*,
+    // sp_genome_reset, sp_genome_add*, sp_count*.
+    struct map_table_t {
+        bool valid = false;
+        int64_t bin_size = 0, chunk_size = 0;
+        int n_sg = 0, k = 0;
+        std::vector<int64_t> slot_off;   // n_chrom + 1 offsets, as the caller passed them
+    } map_table;
     // profiling
     bool prof = false;
     std::vector<sp_prof_entry> prof_pending;
     std::map<std::string, std::pair<int64_t, double>> prof_acc;
     std::map<std::string, int64_t> prof_grid;   // per kernel name: the largest grid (x * y * z workgroups) launched since sp_prof_reset
 };
+
+inline void sp_map_table_drop(sp_ctx *ctx) { ctx->map_table.valid = false; }
 
 extern thread_local std::string g_sp_err;
 

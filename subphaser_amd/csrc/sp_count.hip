@@ -637,6 +637,7 @@ static int count_impl(sp_ctx *ctx, int k, int lower_count, int engine, int first
     SP_HIP(ctx, hipSetDevice(ctx->device));
     if (first < 0 || last > (int)ctx->chroms.size() || first > last)
         return sp_fail(ctx, SP_EINVAL, "sp_count_range: bad chromosome range [%d, %d)", first, last);
+    sp_map_table_drop(ctx);      // (a count may change k: the table sp_map_bins_all left is no longer described by the context)
     if (k > 15) {   // 64-bit keys: sparse engines (engine 1 = device-wide radix sort, otherwise the MSD partition)
         if (first != 0 || last != (int)ctx->chroms.size())
             return sp_fail(ctx, SP_EUNSUP, "sp_count_range: k > 15 counts all chromosomes at once");

@@ -225,6 +225,7 @@ int sp_genome_reset(sp_ctx *ctx, int n_chrom) {
     SP_HIP(ctx, hipSetDevice(ctx->device));
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     sp_blocks_drop(ctx, -1);
+    sp_map_table_drop(ctx);
     if ((size_t)n_chrom == ctx->chroms.size()) {
         // same shape as before: keep every device buffer (packed genome, tables) for reuse
         for (auto &c : ctx->chroms) {
@@ -334,6 +335,7 @@ k0_unpack(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, int6
 static int genome_add_impl(sp_ctx *ctx, int chrom, const uint8_t *d_ascii, int64_t len) {
     sp_chrom &c = ctx->chroms[(size_t)chrom];
     sp_blocks_drop(ctx, chrom);
+    sp_map_table_drop(ctx);
     c.len = len;
     c.length_sum = 0;
     c.n_dump = 0;

@@ -1158,6 +1158,7 @@ static int labels_set_impl(sp_ctx *ctx, const uint64_t *keys, const uint8_t *sg,
     }
     sp_label_plan plan = sp_label_plan_make(ctx->k, n, n_sg, ctx->nslots, sp_label_env_read());
     ctx->labels.ready = false;
+    sp_map_table_drop(ctx);      // the columns of sp_map_bins_all's table were the previous set's subgenomes
     ctx->n_sg = n_sg;
     ctx->n_labels = n;
     // direct table: the previous label set (same k, same buffer) is un-built key by key instead of memset -- while its
@@ -1230,7 +1231,7 @@ int sp_map_bins(sp_ctx *ctx, int chrom, int64_t bin_size, int64_t chunk_size, in
     if (nslots < need) return sp_fail(ctx, SP_EINVAL, "sp_map_bins: nslots %lld < %lld", (long long)nslots, (long long)need);
     const size_t bytes = (size_t)nslots * S * sizeof(int);
     const size_t bytes8 = (bytes + 7) & ~(size_t)7;
-    ctx->map_all_valid = false;
+    sp_map_table_drop(ctx);      // b_map is re-used
     int rcb = sp_buf_ensure(ctx, ctx->b_map, (int64_t)bytes8 + 8);
     if (rcb) return rcb;
     int *d_counts = (int *)ctx->b_map.p;
@@ -1266,6 +1267,7 @@ int sp_map_bins_all(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, const int
     const int64_t total = slot_off[C];
     const size_t bytes = (size_t)total * S * sizeof(int);
     const size_t bytes8 = (bytes + 7) & ~(size_t)7;
+    sp_map_table_drop(ctx);
     int rcb = sp_buf_ensure(ctx, ctx->b_map, (int64_t)(bytes8 + 8 * (size_t)C));
     if (rcb) return rcb;
     int *d_counts = (int *)ctx->b_map.p;
@@ -1286,7 +1288,38 @@ int sp_map_bins_all(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, const int
     SP_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (n_mapped)
         for (int i = 0; i < C; i++) n_mapped[i] = (int64_t)hn[(size_t)i];
-    ctx->map_all_valid = true;   // b_map holds the slot counts of every chromosome (for sp_stack_windows)
+    // b_map holds the slot counts of every chromosome: what the stack entries must be told again
+    ctx->map_table.bin_size = bin_size;
+    ctx->map_table.chunk_size = chunk_size;
+    ctx->map_table.n_sg = S;
+    ctx->map_table.k = ctx->k;
+    ctx->map_table.slot_off.assign(slot_off, slot_off + C + 1);
+    ctx->map_table.valid = true;
+    return SP_OK;
+}
+
+// The stack entries read the table sp_map_bins_all left in b_map, with the caller's description of it: a description
+// that differs from the one the table was made with is refused before anything is launched (a larger bin_size alone
+// would put windows behind the caller's table).
+static int stack_need_table(sp_ctx *ctx, const char *entry, int64_t bin_size, int64_t chunk_size, const int64_t *slot_off) {
+    const sp_ctx::map_table_t &T = ctx->map_table;
+    if (!T.valid) return sp_fail(ctx, SP_EINVAL, "%s: call sp_map_bins_all first", entry);
+    const int C = (int)ctx->chroms.size();
+    if ((size_t)C + 1 != T.slot_off.size())
+        return sp_fail(ctx, SP_EINVAL, "%s: %d chromosomes, sp_map_bins_all mapped %d", entry, C, (int)T.slot_off.size() - 1);
+    if (ctx->n_sg != T.n_sg || ctx->k != T.k)
+        return sp_fail(ctx, SP_EINVAL, "%s: n_sg %d, k %d, sp_map_bins_all mapped with n_sg %d, k %d", entry, ctx->n_sg, ctx->k,
+                       T.n_sg, T.k);
+    if (bin_size != T.bin_size)
+        return sp_fail(ctx, SP_EINVAL, "%s: bin_size %lld, sp_map_bins_all mapped with %lld", entry, (long long)bin_size,
+                       (long long)T.bin_size);
+    if (chunk_size != T.chunk_size)
+        return sp_fail(ctx, SP_EINVAL, "%s: chunk_size %lld, sp_map_bins_all mapped with %lld", entry, (long long)chunk_size,
+                       (long long)T.chunk_size);
+    for (int i = 0; i <= C; i++)
+        if (slot_off[i] != T.slot_off[(size_t)i])
+            return sp_fail(ctx, SP_EINVAL, "%s: slot_off[%d] = %lld, sp_map_bins_all mapped with %lld", entry, i,
+                           (long long)slot_off[i], (long long)T.slot_off[(size_t)i]);
     return SP_OK;
 }
 
@@ -1297,7 +1330,7 @@ int sp_stack_windows_dev(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, int6
                          const int64_t *win_off, const int64_t *seg_start, void *d_win) {
     if (!ctx || !slot_off || !win_off || !d_win || bin_size < 1 || chunk_size < 0 || window_size < 1)
         return sp_fail(ctx, SP_EINVAL, "sp_stack_windows_dev: bad arguments");
-    if (!ctx->map_all_valid) return sp_fail(ctx, SP_EINVAL, "sp_stack_windows: call sp_map_bins_all first");
+    if (stack_need_table(ctx, "sp_stack_windows_dev", bin_size, chunk_size, slot_off)) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     const int C = (int)ctx->chroms.size();
     const int S = ctx->n_sg;
@@ -1331,7 +1364,7 @@ int sp_stack_windows(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, int64_t 
                      const int64_t *slot_off, const int64_t *win_off, int64_t *win_counts) {
     if (!ctx || !slot_off || !win_off || !win_counts || bin_size < 1 || chunk_size < 0 || window_size < 1)
         return sp_fail(ctx, SP_EINVAL, "sp_stack_windows: bad arguments");
-    if (!ctx->map_all_valid) return sp_fail(ctx, SP_EINVAL, "sp_stack_windows: call sp_map_bins_all first");
+    if (stack_need_table(ctx, "sp_stack_windows", bin_size, chunk_size, slot_off)) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = stack_check(ctx, window_size, win_off);
     if (rc) return rc;
@@ -1356,7 +1389,7 @@ int sp_stack_enrich(sp_ctx *ctx, int64_t bin_size, int64_t chunk_size, int64_t w
     if (!ctx || !slot_off || !win_off || !win_counts || !pvals || !argmin || !sig || !ratios || bin_size < 1 ||
         chunk_size < 0 || window_size < 1)
         return sp_fail(ctx, SP_EINVAL, "sp_stack_enrich: bad arguments");
-    if (!ctx->map_all_valid) return sp_fail(ctx, SP_EINVAL, "sp_stack_enrich: call sp_map_bins_all first");
+    if (stack_need_table(ctx, "sp_stack_enrich", bin_size, chunk_size, slot_off)) return SP_EINVAL;
     SP_HIP(ctx, hipSetDevice(ctx->device));
     int rc = stack_check(ctx, window_size, win_off);
     if (rc) return rc;
