@@ -25,49 +25,10 @@
 // Bytes per key (k = 21): 0.375 x 3 scans + 4 w + 4 r + 4 r + 4 w + 4 r  ~ 21 B against ~100 B.
 #include "sp_device.h"
 #include "sp_c2plan.h"      // sp_lanes_fit
+#include "sp_s3plan.h"      // s3_plan, the tile sizes and the finish kernels' thresholds
 #include "sp_internal.h"
 
 #define S3_MAXF 1024
-#define S3_P1_UNIT 32
-#ifndef S3_P2_THREADS
-#define S3_P2_THREADS 512
-#endif
-#ifndef S3_P2_PER
-#define S3_P2_PER 16
-#endif
-#define S3_P2_KEYS (S3_P2_THREADS * S3_P2_PER)   // keys per part2 / hist2 tile
-#define S3_SORT_THREADS 256
-#ifndef S3_SORT_PER
-#define S3_SORT_PER 8      // (16: s3_final 140 -> 131 ms per wheat-like pass at k = 21, but 11 -> 16 ms at k = 17 and more big-list buckets)
-#endif
-#define S3_SORT_CAP (S3_SORT_THREADS * S3_SORT_PER)   // keys one workgroup sorts
-
-struct s3_plan {
-    int T, B1, B2, R1, R2, F1, F2;
-    bool wide1, wide2;   // residuals after level 1 / level 2 need 64 bits
-};
-
-static s3_plan s3_make_plan(int k) {
-    s3_plan p;
-    p.T = 2 * k;
-    p.B1 = 10;   // k <= 21: the residual (2k - 10 bits) fits 32 bits
-#ifndef S3_B2
-#define S3_B2 9
-#endif
-    // Round 6: k = 16 / 17 split level 2 into 2^8 instead of 2^9: the bitmap finish takes 16-bit residuals anyway, and with
-    // half as many fine buckets of twice the keys (2.6 K on a wheat-sized chromosome) s3_part2 writes runs of twice the
-    // length and every per-bucket step of the finish -- seven barriers, two block scans -- is paid half as often:
-    // wheat-like k = 17 pass 213.2 -> 195.5 ms (s3_part2 149 -> 115 ms of events).  k >= 18 (hash finish) stays at 2^9:
-    // 2^8 sends its buckets past the table's capacity (k = 21: 429 ms), 2^10 is slower as well (228 against 220).
-    p.B2 = k <= 17 ? 8 : S3_B2;
-    p.R1 = p.T - p.B1;
-    p.R2 = p.R1 - p.B2;
-    p.F1 = 1 << p.B1;
-    p.F2 = 1 << p.B2;
-    p.wide1 = p.R1 > 32;
-    p.wide2 = p.R2 > 32;
-    return p;
-}
 
 // block-wide exclusive scan of hist[0..F) (F <= 1024) -> start[]; returns the total
 template <int THREADS>
@@ -136,7 +97,6 @@ __device__ __forceinline__ uint32_t s3_scan_reg_t(uint32_t v, uint32_t *wsum /* 
 // the chromosome is counted again from the exact histograms.
 #define S3_STRIPE 64
 #define S3_SAMPLE_SHIFT 4
-#define S3_SAMPLE_MIN_LEN (1LL << 24)     // shorter chromosomes: exact level-1 histogram (and the key count with it)
 __device__ __forceinline__ int64_t s3_sample_unit(int64_t j, int sample_shift) {
     if (sample_shift == 0) return j;
     const int64_t g = j / S3_STRIPE;
@@ -549,12 +509,6 @@ s3_part2(const KR1 *__restrict__ buf1, const unsigned long long *__restrict__ of
 // directly in LDS when <= 13 residual bits are left (always the case for k <= 21), is a single hot key, or
 // sends the whole bucket to the device-wide fallback.  Kept (residual, count) pairs are written at the
 // bucket's own offset of the scratch arrays in ascending order, their number into kept[bucket].
-#define S3_SPLIT_BITS 8
-#define S3_DIRECT_BITS 12
-
-#define S3_SMALL_PER 8
-#define S3_SMALL_CAP (S3_SORT_THREADS * S3_SMALL_PER)   // buckets up to this size take the light kernel
-
 template <typename KR2, int PER>
 struct s3_sort_lds {
     KR2 s[S3_SORT_THREADS * PER];
@@ -562,14 +516,6 @@ struct s3_sort_lds {
     uint32_t wsum[S3_SORT_THREADS / 64], cnt1[S3_SORT_THREADS], cnt2[S3_SORT_THREADS];
 };
 
-#define S3_HASH_SLOTS 2048                       // LDS hash table of the hot-key path
-#define S3_HASH_MAX (S3_HASH_SLOTS * 3 / 4)      // distinct residuals it accepts
-
-// (s3_final_hash's table -- described at the kernel below -- is also what s3_final counts its pieces with)
-#define S3H_COUNTERS 4096
-#define S3H_SLOTS 2048
-#define S3H_CAP 1536            // distinct residuals the table accepts
-#define S3H_PER 8               // keys per thread held in registers: buckets up to 2048 keys are read once
 template <typename KR2>
 struct __attribute__((aligned(16))) s3h_lds {
     union __attribute__((aligned(16))) {
@@ -948,12 +894,6 @@ s3_final_small(const KR2 *__restrict__ buf2, const ulonglong2 *__restrict__ span
 // (s3_final_small + s3_final were 200 of the 507 ms of a wheat-like pass at k = 17; this kernel + the rest of
 // s3_final: 86 ms.  PMC: VALU 43 % and LDS 45 % busy, half of the LDS cycles bank conflicts of the random bitmap /
 // counter accesses; a variant whose first-arriving copy writes the pair out instead of the bit walk was no faster).
-#define S3_BM_MAXBITS 16
-#ifndef S3_BM_CAP
-#define S3_BM_CAP 4096      // distinct residuals per bucket this kernel takes (cnt[] entries); beyond: s3_final
-#endif
-#define S3_BM_NMAX (1u << 22)   // keys per bucket it is willing to stream (hot buckets: few distinct, many copies)
-#define S3_BM_PER 8             // keys per thread prefetched into registers (buckets up to 2048 keys never re-read)
 #define S3_BM_PUNT (~0ULL)      // kept[bucket] value that hands the bucket to s3_final
 // ... and the bucket goes on the punt list s3_final walks (thread 0 of the workgroup; round 3: s3_final used to look at
 // kept[] of all 2^19 buckets, 32 per workgroup with two dependent loads each -- most of its time)
@@ -1318,9 +1258,7 @@ s3_final(const KR2 *__restrict__ buf2, KR2 *__restrict__ scratch, const ulonglon
         unsigned long long bsum = 0;         // their counts; dropped if the bucket goes to the fallback
         if (!give_up) {
             const uint32_t n = (uint32_t)n64;
-            int sb = 1;                      // pieces of ~2 K residuals: a few sorts, not 2^10 tiny ones
-            while (sb < S3_SPLIT_BITS && (n >> sb) > S3_SORT_CAP / 2) sb++;
-            if (sb > R2) sb = R2;
+            S3_SPLIT_BITS_LOOP(sb, n, R2);      // (sp_s3plan.h: the text s3_split_bits wraps for the host)
             const int rem = R2 - sb, nsub = 1 << sb;
             const KR2 rem_mask = (rem >= (int)(8 * sizeof(KR2))) ? (KR2)~(KR2)0 : (KR2)(((KR2)1 << rem) - 1);
             for (int i = threadIdx.x; i < nsub; i += S3_SORT_THREADS) L.sub_cnt[i] = 0;
@@ -1556,9 +1494,6 @@ s3_big_rle(const KR2 *__restrict__ sorted, const unsigned long long *__restrict_
 // orders a bucket's kept list (a bitonic sort in LDS) and writes it where every finish kernel writes.  A class that
 // overflows the table or a kept list beyond S3B_KCAP raises a flag and the library path below takes the chromosome's
 // oversized buckets as before (wheat-like: never).
-#define S3B_SPREAD 32
-#define S3B_KCAP 4096
-#define S3B_MAXBIG 1024         // more oversized buckets than this per chromosome: the library path
 __device__ __forceinline__ uint32_t s3b_class(unsigned long long key, uint32_t P) {
     key ^= key >> 33;
     key *= 0xFF51AFD7ED558CCDULL;
@@ -1749,9 +1684,6 @@ static int s3_scan(sp_ctx *ctx, unsigned long long *a, int64_t n, unsigned long 
 }
 
 // ================================================================== host side
-#ifndef S3_P1T32
-#define S3_P1T32 512
-#endif
 // One chromosome's chain in three phases, so that several chains can be in flight on several streams (round 4: a chain
 // is ~20 launches, several of them one workgroup or latency-bound finish kernels, and used to end in three host
 // synchronisations during which the chip idled):
@@ -1852,7 +1784,7 @@ static int s3_chain_a(sp_ctx *ctx, sp_chrom &c, sp_sparse_chrom &out, const s3_p
             cap_tot = nv;
         }
     }
-    constexpr int P1T_ = sizeof(KR1) == 4 ? S3_P1T32 : 256;
+    constexpr int P1T_ = sizeof(KR1) == 4 ? S3_P1T32 : S3_P1T64;
     const size_t l1_entries = (size_t)cap1 + (size_t)P1T_ * S3_P1_UNIT + 64;      // regions + the trash area of one tile
     const size_t a_bytes = l1_entries * sizeof(KR1) > (size_t)cap_tot * sizeof(KR2) ? l1_entries * sizeof(KR1) : (size_t)cap_tot * sizeof(KR2);
     rc = sp_buf_ensure(ctx, S3_LANE_BUF(ctx, b_sp_a), (int64_t)a_bytes + 64);      // level-1 records, later the finish kernels' scratch (region-indexed)
@@ -1867,7 +1799,7 @@ static int s3_chain_a(sp_ctx *ctx, sp_chrom &c, sp_sparse_chrom &out, const s3_p
     KR2 *tmp_keys = (KR2 *)S3_LANE_BUF(ctx, b_sp_c).p;
     uint32_t *tmp_cnts = (uint32_t *)((char *)S3_LANE_BUF(ctx, b_sp_c).p + tk_bytes);
 
-    constexpr int P1T = sizeof(KR1) == 4 ? S3_P1T32 : 256;
+    constexpr int P1T = sizeof(KR1) == 4 ? S3_P1T32 : S3_P1T64;
     const int64_t n_units32 = (len + S3_P1_UNIT - 1) / S3_P1_UNIT;
     const int64_t n_tiles1 = (n_units32 + P1T - 1) / P1T;
     int64_t g1 = n_tiles1 < (int64_t)ctx->n_cu * 8 ? n_tiles1 : (int64_t)ctx->n_cu * 8;

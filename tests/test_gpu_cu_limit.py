@@ -28,13 +28,13 @@ work exceeded it.
     c2_count16 (sp_count2.hip:1598)               2                    1024 / 16 384 buckets (k = 13 / 15)  >= 3 passes
     batched chain (sp_count2.hip:1713 cap_grid)   ceil(limit * per_cu / 3) x 3 chromosomes, per_cu = 2, 8, 8 for
       c2_hist_sample, c2_part1, c2_part2                               3 / 7, 41 / 101, 683 or more tiles   >= 2 passes
-    s3_hist1 (sp_sparse2.hip:1810)                8                    81 / 201 blocks of 256 units         >= 3 passes
-    s3_part1 (sp_sparse2.hip:1873)                8                    41 / 101 tiles (81 / 201 at k = 22)  >= 3 passes
-    s3_hist2_sample (sp_sparse2.hip:1881)         8                    1104 / 1223 tiles at most            >= 2 passes
-    s3_part2 (sp_sparse2.hip:1892)                16                   1104 / 1223 tiles at most            >= 2 passes
-    s3_final_bitmap, s3_final_hash (:1910)        64                   262 144 / 524 288 buckets (k 17/22)  >= 3 passes
-    s3_final (sp_sparse2.hip:1928)                8                    the same buckets                     >= 3 passes
-    s3_gather (sp_sparse2.hip:2063)               32                   a block for every four buckets       >= 3 passes
+    s3_hist1 (sp_sparse2.hip:1742)                8                    81 / 201 blocks of 256 units         >= 3 passes
+    s3_part1 (sp_sparse2.hip:1805)                8                    41 / 101 tiles (81 / 201 at k = 22)  >= 3 passes
+    s3_hist2_sample (sp_sparse2.hip:1813)         8                    1104 / 1223 tiles at most            >= 2 passes
+    s3_part2 (sp_sparse2.hip:1824)                16                   1104 / 1223 tiles at most            >= 2 passes
+    s3_final_bitmap, s3_final_hash (:1842)        64                   262 144 / 524 288 buckets (k 17/22)  >= 3 passes
+    s3_final (sp_sparse2.hip:1860)                8                    the same buckets                     >= 3 passes
+    s3_gather (sp_sparse2.hip:1995)               32                   a block for every four buckets       >= 3 passes
     sps_keygen (sp_sparse.hip:872)                16                   41 / 101 blocks of 256 units         >= 2 passes
     sps_join (sp_listfilter.hip:1105)             16                   32 / 64 key ranges                   >= 2 passes
     sps_join_wide (sp_listfilter.hip:1105)        16                   64 / 256 key ranges of 130 lists     >= 3 passes
@@ -68,7 +68,8 @@ Not covered -- these never reach their cap here, or no stage of this file calls 
     c2_count (sp_count2.hip:1565): runs only under SP_C2_COUNT16=0;
     c2_count_list (sp_count2.hip:1579/1733): at most 256 buckets a workgroup, which sets its grid above the cap;
     s3_hist1_sample, s3_hist2, s3_final_small (the sites of s3_hist1, s3_hist2_sample and s3_final_bitmap under other
-    names): chromosomes long enough to sample, SP_S3_EXACT=1, SP_S3_FINAL=sort."""
+    names): chromosomes long enough to sample, SP_S3_EXACT=1, SP_S3_FINAL=sort (s3_hist2 and s3_final_small run, below
+    their caps, in test_gpu_sparse_paths.py: every small case under SP_S3_EXACT=1, the sort_size_classes cases)."""
 import contextlib
 
 import numpy as np

@@ -264,8 +264,12 @@ def test_count_sparse_engine_sampled_sizing_and_recount(gpu_ctx, monkeypatch):
 def test_count_sparse_engine_lanes_and_oversized_paths(gpu_ctx, monkeypatch):
     """round 4: (a) several chromosome chains in flight (three phases on SP_LANES_SPARSE streams) against one chain at a
     time; (b) every bucket above one sort's worth of keys forced through the oversized path (test hook): cut by hash
-    class (s3_big_class + s3_big_sort) and, as the cross-check, through the library sort (SP_S3_BIG=sort); (c) a kept
-    list beyond the class path's capacity must fall back to the library path.  All against the oracle."""
+    class (s3_big_class + s3_big_sort) and, as the cross-check, through the library sort (SP_S3_BIG=sort); (c) one fine
+    bucket with 3000 and with 6000 distinct residuals of count 2.  By the routing model of tests/s3_cases.py neither reaches
+    the oversized paths: s3_final_hash hands the bucket over (more than 1536 distinct), s3_final splits it on 3 / 4 bits
+    into 4 / 8 pieces of about 1500 keys and 750 distinct residuals, and each piece is finished by the hashed count.  The
+    give-up list, the hash classes and the fall-back to the library path beyond the class path's list are reached, with
+    the evidence of the kernels that ran, by the give_up_* cases of test_gpu_sparse_paths.py.  All against the oracle."""
     rng = np.random.RandomState(404)
     unit = _rand_seq(rng, 29, 0, 0)
     seqs = [np.concatenate([_rand_seq(rng, 250_000), np.tile(unit, 4000), _rand_seq(rng, 40_000)]),
@@ -286,8 +290,8 @@ def test_count_sparse_engine_lanes_and_oversized_paths(gpu_ctx, monkeypatch):
     monkeypatch.delenv("SP_S3_BIG")
     monkeypatch.delenv("SP_S3_FORCE_BIG")
     # (c) ONE fine bucket with thousands of distinct residuals of count 2: blocks `AAAAAAAAAA + k - 10 random bases + N`
-    # hold one valid k-mer each, all with the same leading 20 bits.  3000 distinct: more than the finish kernels' tables
-    # take -> the hash classes; 6000: more kept pairs than the class path's list holds -> the library path
+    # hold one valid k-mer each, all with the same leading 20 bits.  3000 and 6000 distinct: more than s3_final_hash's table
+    # takes -> s3_final, split into pieces of ~1500 keys, each counted by the hashed path (see the docstring)
     for k in (21, 31):
         for distinct in (3000, 6000):
             body = np.frombuffer(b"ACGT", np.uint8)[rng.randint(0, 4, size=(distinct, k - 10))]
