@@ -1,8 +1,10 @@
 // sp_map.h -- what the dense (sp_map.hip) and the sparse (sp_sparse.hip) map stages share: the pair
-// filter, the pair-table field layout, the output-slot arithmetic of Seqs.map_kmer3's chunks and bins.
+// filter, the pair-table field layout, the walkers' interface and the one consumer per walk mode (bins, features, intervals).
+// The integer rules of the modes (output slots of Seqs.map_kmer3's chunks and bins, feature cursor, plane masks): sp_mapslots.h.
 #pragma once
 #include "sp_device.h"
 #include "sp_maphash.h"
+#include "sp_mapslots.h"
 
 #ifndef MAP_BLOOM_MAX_BITS
 #define MAP_BLOOM_MAX_BITS 25
@@ -208,12 +210,6 @@ __host__ __device__ __forceinline__ int map_ct_sites(uint64_t o, int k, map_ct_s
 #ifndef MAP_GRID_MULT
 #define MAP_GRID_MULT 16
 #endif
-#ifndef MAP_BLOCK
-#define MAP_BLOCK 512   // rounds 2-5 (one-phase walks): 256 -> 70.5 ms, 512 -> 68.3, 768 -> 66.2, 1024 -> 73.8.  Round 6 (two-phase walk,
-                        // bound by waiting, not by instruction issue): 768 x 2 workgroups per CU (6 waves per SIMD) 34.5 ms,
-                        // 512 x 4 (8 per SIMD, 64 VGPRs) 32.6, 256 x 8 33.0, 384 x 5 35.4, 1024 x 2 33.6
-#endif
-#define MAP_RANGE (MAP_BLOCK * SP_UNIT)  // starts per block iteration
 // the grid of every map walk, k <= 15 and k > 15: a workgroup per range of MAP_BLOCK units, MAP_GRID_MULT per compute unit at most
 inline int64_t map_grid(const sp_ctx *ctx, int64_t n_ranges) {
     const int64_t cap = (int64_t)ctx->n_cu * MAP_GRID_MULT;
@@ -239,59 +235,198 @@ struct map_unit_lds {
     __shared__ uint16_t s_uq[(MAP_BLOCK / 64) * MAP_QCAP(TABLE)];                         \
     const map_unit_lds ulds = {s_uw, s_up, s_uq}
 
-#ifndef MAP_LDS_ENTRIES
-#define MAP_LDS_ENTRIES 1024      // (4096 until round 6: the LDS went to the walk's candidate queue; a range of 49 152 starts needs
-                                   // ~ 10 x S entries at 10-kb bins, 1024 cover bins down to ~150 bases at S = 3 -- below that: global atomics)
-#endif
-
-struct sp_map_params {
-    int64_t n_units;
-    int64_t bin_size;
-    int64_t chunk_size;
-    int64_t nslots;
-    int S;
-    int use_lds;
+// ----------------------------------------------------------------- walkers and consumers
+// A map kernel pairs a WALKER -- how a unit of 64 starts is answered from the label table -- with a CONSUMER -- what its walk
+// mode does with the answer.  Two flavours of answer:
+//   planes  walk(s0, lab, U, cm): three 64-bit label planes of the unit, bit j = the label bits of start s0 + j; only the starts
+//           in `cm` are counted and marked "seen" (the two-phase walks: map_walk_pair in sp_map.hip, sps_walk_pair in sp_sparse.hip);
+//   hits    walk.scan(s0, each): each(start, key) for every valid start that passes the filter, and walk.look(key, counted):
+//           the subgenome of `key` or -1.  `counted` is asked at most once, and the k-mer is marked "seen" only where it
+//           holds: a walker that can look before it marks asks it after the look-up, one whose look-up marks asks it first
+//           (map_walk_bytes in sp_map.hip, sps_walk_kmer in sp_sparse.hip).
+// Every consumer below exists once; everything is inlined into the twelve kernels.  Walkers and the bins accumulator hold
+// the kernel's by-value arguments (k-mer parameters, table, map parameters) by reference: they never outlive its frame.
+struct map_always {
+    __device__ __forceinline__ bool operator()() const { return true; }
 };
 
-__device__ __forceinline__ int64_t map_slot(int64_t s, const sp_map_params &P, int k) {
-    int64_t chunk = 0;
-    if (P.chunk_size > 0 && s >= P.chunk_size - (k - 1)) chunk = (s + (k - 1)) / P.chunk_size;
-    return s / P.bin_size + chunk;
-}
+// ---- bins: counts[slot][sg] of one chromosome.  One accumulator per thread; a workgroup takes ranges of MAP_BLOCK units
+// through begin() / end() (block-uniform calls: they hold barriers), a range's hits go to the LDS histogram over the few
+// output slots it touches (P.use_lds: map_params_of) and from there to the table with one atomic per non-zero entry.
+// (the histogram's pointer keeps its address space in its type: as a generic pointer the compiler merges the LDS atomic with
+// the global one of the other branch into one flat atomic on a selected address)
+typedef __attribute__((address_space(3))) int map_lds_int;
+struct map_bins_acc {
+    map_lds_int *hist;              // [MAP_LDS_ENTRIES]
+    const sp_map_params &P;         // the kernel's argument: the accumulator lives inside one kernel's frame, as the walkers do
+    int k;
+    int *counts = nullptr;          // [nslots x S]: the table of the range's chromosome
+    int64_t nslots = 0;
+    int64_t slot_lo = 0;            // the range's first output slot
+    bool one_slot = false;          // ... is its only one (uniform; found once per range, not per hit)
+    unsigned long long mapped = 0;  // hits this thread has counted
 
-// first start after `s` whose output slot differs from map_slot(s) (next bin or next chunk boundary)
-__device__ __forceinline__ int64_t map_slot_end(int64_t s, const sp_map_params &P, int k) {
-    int64_t e = (s / P.bin_size + 1) * P.bin_size;
-    if (P.chunk_size > 0) {
-        const int64_t chunk = (s >= P.chunk_size - (k - 1)) ? (s + (k - 1)) / P.chunk_size : 0;
-        const int64_t c = (chunk + 1) * P.chunk_size - (k - 1);
-        e = c < e ? c : e;
-    }
-    return e;
-}
-
-// feature mode: per-feature totals.  The features lie back to back in one packed sequence (no
-// separators): a k-mer belongs to feature f iff it lies entirely inside [foff[f], foff[f+1]).  The
-// feature of a unit's first hit is found by binary search, later hits of the unit walk forward.
-struct map_feat_cursor {
-    int64_t f, next;   // current feature and foff[f + 1]; f < 0: not located yet
-};
-__device__ __forceinline__ bool map_feat_locate(map_feat_cursor &c, int64_t start, int k,
-                                                const int64_t *__restrict__ foff, int64_t n_feat) {
-    if (c.f < 0) {
-        int64_t lo = 0, hi = n_feat;   // last f with foff[f] <= start
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (foff[mid] <= start) lo = mid;
-            else hi = mid;
+    __device__ __forceinline__ map_bins_acc(int *hist_, const sp_map_params &P_, int k_) : hist((map_lds_int *)hist_), P(P_), k(k_) {}
+    __device__ __forceinline__ void begin(int64_t r, int *counts_, int64_t nslots_) {
+        counts = counts_;
+        nslots = nslots_;
+        slot_lo = map_slot(r * MAP_RANGE, P, k);
+        one_slot = map_slot_end(r * MAP_RANGE, P, k) >= (r + 1) * MAP_RANGE;
+        if (P.use_lds) {
+            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) hist[i] = 0;
+            __syncthreads();
         }
-        c.f = lo;
-        c.next = foff[lo + 1];
     }
-    while (start >= c.next && c.f + 1 < n_feat) {
-        c.f++;
-        c.next = foff[c.f + 1];
+    __device__ __forceinline__ void end() {
+        if (P.use_lds) {
+            __syncthreads();
+            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) {
+                int v = hist[i];
+                if (v) {
+                    int64_t os = slot_lo + i / P.S;
+                    if (os < nslots) atomicAdd(&counts[os * P.S + (i % P.S)], v);
+                }
+            }
+            __syncthreads();
+        }
     }
-    return start + k <= c.next;        // false: the k-mer runs into the next feature
+    __device__ __forceinline__ void add(int64_t os, int sg, int v) {
+        if (P.use_lds) atomicAdd((int *)&hist[(int)(os - slot_lo) * P.S + sg], v);
+        else if (os < nslots) atomicAdd(&counts[os * P.S + sg], v);
+        mapped += v;
+    }
+    // hits: every labelled start a hits walker finds in the unit at s0
+    template <typename Walk>
+    __device__ __forceinline__ void add_hits(const Walk &walk, int64_t s0) {
+        walk.scan(s0, [&](int64_t start, auto key) {
+            const int sg = walk.look(key, map_always());
+            if (sg >= 0) add(map_slot(start, P, k), sg, 1);
+        });
+    }
+    // the hits of the unit at s0 among the starts `within` -> slot os
+    __device__ __forceinline__ void add_within(int64_t os, const unsigned long long lab[3], unsigned long long within) {
+        for (int sg = 0; sg < P.S; sg++) {
+            const int v = __popcll(map_plane_mask(lab, sg) & within);
+            if (v) add(os, sg, v);
+        }
+    }
+    __device__ __forceinline__ void add_planes(int64_t s0, const unsigned long long lab[3]) {
+        if (!(lab[0] | lab[1] | lab[2])) return;
+        if (one_slot) {
+            add_within(slot_lo, lab, ~0ULL);
+            return;
+        }
+        int64_t p = s0;
+        while (p < s0 + SP_UNIT) {
+            int64_t e = map_slot_end(p, P, k);
+            if (e > s0 + SP_UNIT) e = s0 + SP_UNIT;
+            const unsigned long long within = map_span(p - s0, e - s0);      // starts [p, e) of the unit
+            if ((lab[0] | lab[1] | lab[2]) & within) add_within(map_slot(p, P, k), lab, within);
+            p = e;
+        }
+    }
+};
+
+// the bins of ONE chromosome per launch (all but k5_map2): unit(s0) answers the unit at s0 into the accumulator
+template <typename Unit>
+__device__ __forceinline__ void map_bins_chrom(map_bins_acc &acc, unsigned long long *red /* [16], LDS */, int *counts,
+                                               unsigned long long *n_mapped, Unit &&unit) {
+    const int64_t n_ranges = (acc.P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
+    for (int64_t r = blockIdx.x; r < n_ranges; r += gridDim.x) {
+        const int64_t u = r * MAP_BLOCK + threadIdx.x;
+        acc.begin(r, counts, acc.P.nslots);
+        if (u < acc.P.n_units) unit(u * SP_UNIT);
+        acc.end();
+    }
+    const unsigned long long t = sp_block_sum_u64(acc.mapped, red);
+    if (threadIdx.x == 0 && t) atomicAdd(n_mapped, t);
 }
 
+// ---- features: counts[f][sg].  Planes, per unit: (1) the starts whose k-mer crosses no feature boundary (`fit`) -- only those
+// are scanned, counted and marked "seen", exactly the k-mers a FASTA of the features holds; (2) the label planes of the unit;
+// (3) one walk over the features that overlap the unit: popcounts of the planes inside the feature.
+template <typename Walk>
+__device__ __forceinline__ void map_feat_planes(const Walk &walk, const map_unit_lds &U, int k, int64_t n_units,
+                                                const int64_t *__restrict__ foff, int64_t n_feat, int S,
+                                                unsigned long long *__restrict__ counts) {
+    int64_t u = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * MAP_BLOCK;
+    for (; u < n_units; u += stride) {
+        const int64_t s0 = u * SP_UNIT;
+        int64_t lo;                            // the feature the unit starts in
+        const unsigned long long fit = map_unit_fit(foff, n_feat, s0, k, lo);
+        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
+        walk(s0, lab, U, fit);
+        if (!(lab[0] | lab[1] | lab[2])) continue;
+        // (3) (a start beyond the last feature's end is padding: never valid)
+        for (int64_t f = lo; f < n_feat; f++) {
+            const int64_t a = foff[f], e = foff[f + 1];
+            if (a >= s0 + SP_UNIT) break;
+            const unsigned long long within = map_span((a > s0 ? a : s0) - s0, (e < s0 + SP_UNIT ? e : s0 + SP_UNIT) - s0) & fit;
+            if (!((lab[0] | lab[1] | lab[2]) & within)) continue;
+            for (int sg = 0; sg < S; sg++) {
+                const unsigned long long m = map_plane_mask(lab, sg) & within;
+                if (m) atomicAdd(&counts[f * S + sg], (unsigned long long)__popcll(m));
+            }
+        }
+    }
+}
+// hits: a cursor over the features, per unit; a start counts where the cursor finds its whole k-mer inside one feature
+template <typename Walk>
+__device__ __forceinline__ void map_feat_hits(const Walk &walk, int k, int64_t n_units, const int64_t *__restrict__ foff,
+                                              int64_t n_feat, int S, unsigned long long *__restrict__ counts) {
+    int64_t u = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * MAP_BLOCK;
+    for (; u < n_units; u += stride) {
+        map_feat_cursor cur;
+        cur.f = -1;
+        cur.next = 0;
+        walk.scan(u * SP_UNIT, [&](int64_t start, auto key) {
+            const int sg = walk.look(key, [&]() { return map_feat_locate(cur, start, k, foff, n_feat); });
+            if (sg >= 0) atomicAdd(&counts[cur.f * S + sg], 1ULL);
+        });
+    }
+}
+
+// ---- intervals: masks[u][sg], bit j = the covered start 64 u + j carries a k-mer of subgenome sg (`cov`: kv_cover in
+// sp_map.hip).  Planes: the label planes of a unit, restricted to the covered starts, ARE its masks.
+template <typename Walk>
+__device__ __forceinline__ void map_mask_planes(const Walk &walk, const map_unit_lds &U, int64_t n_units, int S,
+                                                const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks) {
+    int64_t u = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * MAP_BLOCK;
+    for (; u < n_units; u += stride) {
+        const unsigned long long cv = cov[u];
+        if (__all(cv == 0ULL)) continue;         // nothing of this wave's 4096 starts lies in a feature
+        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
+        walk(u * SP_UNIT, lab, U, cv);
+        for (int sg = 0; sg < S; sg++) masks[u * S + sg] = map_plane_mask(lab, sg) & cv;
+    }
+}
+template <typename Walk>
+__device__ __forceinline__ void map_mask_hits(const Walk &walk, int64_t n_units, int S, const unsigned long long *__restrict__ cov,
+                                              unsigned long long *__restrict__ masks) {
+    int64_t u = (int64_t)blockIdx.x * MAP_BLOCK + threadIdx.x;
+    const int64_t stride = (int64_t)gridDim.x * MAP_BLOCK;
+    for (; u < n_units; u += stride) {
+        const unsigned long long cv = cov[u];
+        if (__all(cv == 0ULL)) continue;
+        walk.scan(u * SP_UNIT, [&](int64_t start, auto key) {
+            const unsigned long long bit = 1ULL << (start & 63);
+            if (!(cv & bit)) return;             // not covered: not looked up, so never marked
+            const int sg = walk.look(key, map_always());
+            if (sg >= 0) atomicOr(&masks[u * S + sg], bit);
+        });
+    }
+}
+
+// ---- host: the walker of a label-table kind, as a type.  Each file has ONE switch from ctx->labels.kind to these
+// (map_with_walker in sp_map.hip, sps_with_walker in sp_sparse.hip); a mode's launcher is a generic lambda over them.
+template <int TABLE>
+struct map_planes_of {              // a two-phase walk; TABLE as in map_unit_scan64 / map_unit_scan64_h
+    static constexpr bool planes = true;
+    static constexpr int table = TABLE;
+};
+struct map_hits_of {                // map_pair_scan + a look-up per candidate start
+    static constexpr bool planes = false;
+};

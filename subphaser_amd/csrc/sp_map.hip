@@ -3,6 +3,11 @@
 // Replaces Seqs.map_kmer3 / chunk_chromfiles / map_kmer_each4
 // (reference: subphaser/Seqs.py:74-153, 209-244): every k-mer START position
 // whose canonical k-mer is subgenome-specific adds 1 to (bin of start, SG).
+//
+// The K5 kernels of this file pair a walker of k <= 15 with a consumer of sp_map.h: k5_map2, k5_map_feat2, k5_map_mask2
+// (map_walk_pair: map_unit_scan64 over the direct or the compact pair table, label planes) and k5_map_lab, k5_map_feat_lab,
+// k5_map_mask_lab (map_walk_bytes: map_pair_scan + the byte table, hits).  Their k > 15 twins are in sp_sparse.hip.  One
+// switch (map_with_walker) turns the label table's kind into the walker; a mode's launcher is a generic lambda over it.
 #include "sp_device.h"
 #include "sp_internal.h"
 #include "sp_map.h"
@@ -491,6 +496,20 @@ __device__ __forceinline__ void map_unit_scan64(const uint32_t *__restrict__ pk,
     for (int bit = 0; bit < NP; bit++) lab[bit] = U.planes[bit * MAP_BLOCK + tid];
 }
 
+// the planes walker of k <= 15 (sp_map.h): the two-phase walk over the direct (TABLE 0) or the compact (1) pair table
+template <int TABLE>
+struct map_walk_pair {
+    const uint32_t *pk, *pm, *nm;
+    const sp_kparams32 &kp;
+    const map_ptab &T;
+    const uint32_t *bloom;
+    int nbits;
+    __device__ __forceinline__ void operator()(int64_t s0, unsigned long long lab[3], const map_unit_lds &U,
+                                               unsigned long long cm = ~0ULL) const {
+        map_unit_scan64<TABLE>(pk, pm, nm, s0, kp, bloom, nbits, T, lab, U, cm);
+    }
+};
+
 template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK, MAP_MIN_WAVES)
 k5_map2(const map_chrom_desc *__restrict__ desc, int n_chrom, int64_t n_ranges, sp_kparams32 kp, sp_map_params P,
@@ -498,13 +517,13 @@ k5_map2(const map_chrom_desc *__restrict__ desc, int n_chrom, int64_t n_ranges, 
     __shared__ int hist[MAP_LDS_ENTRIES];
     __shared__ unsigned long long red[16];
     MAP_UNIT_LDS_DECL(TABLE, 7);
-    unsigned long long mapped = 0;
-    int cur = -1;          // chromosome the block is accumulating `mapped` for
+    map_bins_acc acc(hist, P, kp.k);
+    int cur = -1;          // chromosome the block is accumulating `acc.mapped` for
     auto flush_mapped = [&]() {     // block-uniform control flow
         if (cur < 0) return;
-        const unsigned long long t = sp_block_sum_u64(mapped, red);
+        const unsigned long long t = sp_block_sum_u64(acc.mapped, red);
         if (threadIdx.x == 0 && t) atomicAdd(desc[cur].n_mapped, t);
-        mapped = 0;
+        acc.mapped = 0;
     };
     for (int64_t rg = blockIdx.x; rg < n_ranges; rg += gridDim.x) {
         int lo = 0, hi = n_chrom;              // last chromosome with range0 <= rg (uniform: scalar loads)
@@ -520,79 +539,24 @@ k5_map2(const map_chrom_desc *__restrict__ desc, int n_chrom, int64_t n_ranges, 
         const map_chrom_desc D = desc[lo];
         const int64_t r = rg - D.range0;
         const int64_t u = r * MAP_BLOCK + threadIdx.x;
-        // the range's first output slot and where it ends (uniform; once per range, not per hit)
-        const int64_t slot_lo = map_slot(r * MAP_RANGE, P, kp.k), end_lo = map_slot_end(r * MAP_RANGE, P, kp.k);
-        const bool one_slot = end_lo >= (r + 1) * MAP_RANGE;
-        if (P.use_lds) {
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) hist[i] = 0;
-            __syncthreads();
-        }
+        acc.begin(r, D.counts, D.nslots);
         if (u < D.n_units) {
             unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-            map_unit_scan64<TABLE>(D.pk, D.pm, D.nm, u * SP_UNIT, kp, bloom, bloom_bits, ptab, lab, ulds);
-            if (lab[0] | lab[1] | lab[2]) {
-                auto add = [&](int64_t os, unsigned long long within) {       // the unit's hits among the starts `within` -> slot os
-                    for (int sg = 0; sg < P.S; sg++) {
-                        const int l = sg + 1;
-                        const unsigned long long m = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) &
-                                                     ((l & 4) ? lab[2] : ~lab[2]) & within;
-                        const int v = __popcll(m);
-                        if (!v) continue;
-                        if (P.use_lds) atomicAdd(&hist[(int)(os - slot_lo) * P.S + sg], v);
-                        else if (os < D.nslots) atomicAdd(&D.counts[os * P.S + sg], v);
-                        mapped += v;
-                    }
-                };
-                const int64_t s0 = u * SP_UNIT;
-                if (one_slot) {
-                    add(slot_lo, ~0ULL);
-                } else {
-                    int64_t p = s0;
-                    while (p < s0 + SP_UNIT) {
-                        int64_t e = map_slot_end(p, P, kp.k);
-                        if (e > s0 + SP_UNIT) e = s0 + SP_UNIT;
-                        const int a = (int)(p - s0), b = (int)(e - s0);      // starts [a, b) of the unit
-                        const unsigned long long within = (b >= 64 ? ~0ULL : ((1ULL << b) - 1ULL)) & ~((1ULL << a) - 1ULL);
-                        if ((lab[0] | lab[1] | lab[2]) & within) add(map_slot(p, P, kp.k), within);
-                        p = e;
-                    }
-                }
-            }
+            map_walk_pair<TABLE>{D.pk, D.pm, D.nm, kp, ptab, bloom, bloom_bits}(u * SP_UNIT, lab, ulds);
+            acc.add_planes(u * SP_UNIT, lab);
         }
-        if (P.use_lds) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) {
-                int v = hist[i];
-                if (v) {
-                    int64_t os = slot_lo + i / P.S;
-                    if (os < D.nslots) atomicAdd(&D.counts[os * P.S + (i % P.S)], v);
-                }
-            }
-            __syncthreads();
-        }
+        acc.end();
     }
     flush_mapped();
 }
 
-// interval (BED) mode on the rolled walk: the label planes of a unit, restricted to the covered starts, ARE its masks
 template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK, MAP_MIN_WAVES)
 k5_map_mask2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm, sp_kparams32 kp,
              int64_t n_units, int S, map_ptab ptab, const uint32_t *__restrict__ bloom, int bloom_bits,
              const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks /* n_units x S */) {
     MAP_UNIT_LDS_DECL(TABLE, 7);
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        const unsigned long long cv = cov[u];
-        if (__all(cv == 0ULL)) continue;         // nothing of this wave's 4096 starts lies in a feature
-        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-        map_unit_scan64<TABLE>(pk, pm, nm, u * SP_UNIT, kp, bloom, bloom_bits, ptab, lab, ulds, cv);
-        for (int sg = 0; sg < S; sg++) {
-            const int l = sg + 1;
-            masks[u * S + sg] = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) & ((l & 4) ? lab[2] : ~lab[2]) & cv;
-        }
-    }
+    map_mask_planes(map_walk_pair<TABLE>{pk, pm, nm, kp, ptab, bloom, bloom_bits}, ulds, n_units, S, cov, masks);
 }
 
 // the exact pair table the current label set lives in (SP_LABELS_DIRECT or SP_LABELS_COMPACT)
@@ -608,71 +572,43 @@ static map_ptab map_ptab_of(const sp_ctx *ctx) {
     return T;
 }
 
-// the parameters of a bins walk; its LDS histogram serves when the slots a range of MAP_RANGE starts touches fit it
-static sp_map_params map_params_of(int64_t len, int64_t bin_size, int64_t chunk_size, int64_t nslots, int S) {
-    sp_map_params P;
-    P.n_units = (len + SP_UNIT - 1) / SP_UNIT;
-    P.bin_size = bin_size;
-    P.chunk_size = chunk_size;
-    P.nslots = nslots;
-    P.S = S;
-    const int64_t local = MAP_RANGE / bin_size + 3 + (chunk_size > 0 ? MAP_RANGE / chunk_size + 2 : 0);
-    P.use_lds = (local * S <= MAP_LDS_ENTRIES) ? 1 : 0;
-    return P;
-}
-
 // the one readiness test of the map entries (sp_label_state in sp_common.h says when `ready` holds)
 static int map_need_labels(sp_ctx *ctx, const char *entry) {
     if (ctx->labels.ready) return SP_OK;
     return sp_fail(ctx, SP_EINVAL, "%s: call sp_labels_set first", entry);
 }
 
-// K5, label-table engine (any S <= 126; the rolling scan + one byte gather per candidate start)
+// the hits walker of k <= 15 (sp_map.h), any S <= 126: the rolling scan + one byte gather per candidate start from the label
+// table; bit 7 of a label byte is its "seen" mark
+struct map_walk_bytes {
+    const uint32_t *pk, *nm;
+    const sp_kparams32 &kp;
+    uint8_t *label;
+    const uint32_t *bloom;
+    int nbits;
+    template <typename F>
+    __device__ __forceinline__ void scan(int64_t s0, F &&each) const {
+        map_pair_scan<uint32_t>(pk, nm, s0, kp, bloom, nbits,
+                                [&](int64_t start, uint32_t fwd, uint32_t rc) { each(start, sp_slot_of32(fwd, rc, kp)); });
+    }
+    template <typename C>
+    __device__ __forceinline__ int look(uint32_t slot, C &&counted) const {
+        const uint32_t l = label[slot];
+        if (!l || !counted()) return -1;
+        if (!(l & 0x80u)) label[slot] = (uint8_t)(l | 0x80u);  // idempotent "seen" mark
+        return (int)(l & 0x7fu) - 1;
+    }
+};
+
 __global__ void __launch_bounds__(MAP_BLOCK)
 k5_map_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams32 kp,
        sp_map_params P, uint8_t *__restrict__ label, const uint32_t *__restrict__ bloom, int bloom_bits,
        int *__restrict__ slot_counts, unsigned long long *__restrict__ n_mapped) {
     __shared__ int hist[MAP_LDS_ENTRIES];
     __shared__ unsigned long long red[16];
-    unsigned long long mapped = 0;
-    const int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    for (int64_t r = blockIdx.x; r < n_ranges; r += gridDim.x) {
-        const int64_t u = r * MAP_BLOCK + threadIdx.x;
-        const int64_t slot_lo = map_slot(r * MAP_RANGE, P, kp.k);
-        if (P.use_lds) {
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) hist[i] = 0;
-            __syncthreads();
-        }
-        if (u < P.n_units) {
-            map_pair_scan<uint32_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint32_t fwd, uint32_t rc) {
-                const uint32_t slot = sp_slot_of32(fwd, rc, kp);
-                const uint32_t l = label[slot];
-                if (l) {
-                    if (!(l & 0x80u)) label[slot] = (uint8_t)(l | 0x80u);  // idempotent "seen" mark
-                    const int sg = (int)(l & 0x7fu) - 1;
-                    const int64_t os = map_slot(start, P, kp.k);
-                    if (P.use_lds)
-                        atomicAdd(&hist[(os - slot_lo) * P.S + sg], 1);
-                    else if (os < P.nslots)
-                        atomicAdd(&slot_counts[os * P.S + sg], 1);
-                    mapped++;
-                }
-            });
-        }
-        if (P.use_lds) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) {
-                int v = hist[i];
-                if (v) {
-                    int64_t os = slot_lo + i / P.S;
-                    if (os < P.nslots) atomicAdd(&slot_counts[os * P.S + (i % P.S)], v);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    unsigned long long t = sp_block_sum_u64(mapped, red);
-    if (threadIdx.x == 0 && t) atomicAdd(n_mapped, t);
+    const map_walk_bytes walk{pk, nm, kp, label, bloom, bloom_bits};
+    map_bins_acc acc(hist, P, kp.k);
+    map_bins_chrom(acc, red, slot_counts, n_mapped, [&](int64_t s0) { acc.add_hits(walk, s0); });
 }
 
 // Window stack on the device (Circos.stack_matrix semantics, Circos.py:734-742): the window of a
@@ -696,22 +632,13 @@ k5_stack(const int *__restrict__ slot_counts, int64_t total_slots, int S, int C,
         else hi = mid;
     }
     const int64_t slot = gslot - slot_off[lo];
-    int64_t chunk = 0;
-    if (chunk_size > 0) {
-        // first slot of chunk j >= 1: (j*W - (k-1)) / b + j ; chunk(slot) = #{j : first(j) <= slot}
-        chunk = slot * bin_size / (chunk_size + bin_size);
-        while ((((chunk + 1) * chunk_size - (k - 1)) / bin_size + (chunk + 1)) <= slot) chunk++;
-        while (chunk > 0 && ((chunk * chunk_size - (k - 1)) / bin_size + chunk) > slot) chunk--;
-    }
+    const int64_t chunk = chunk_size > 0 ? map_chunk_of_slot(slot, bin_size, chunk_size, k) : 0;
     const int64_t win = ((seg_start ? seg_start[lo] : 0) + (slot - chunk) * bin_size) / window_size;
     atomicAdd(&win_counts[(win_off[lo] + win) * S + sg], (unsigned long long)v);
 }
 
-// Feature mode on the rolled walk (round 6; it ran on the unrolled walk of rounds 2-4 until then).  The features lie back to
-// back in one packed sequence; a k-mer belongs to feature f iff it lies entirely inside [foff[f], foff[f + 1]).  Per unit of
-// 64 starts: (1) the starts whose k-mer crosses no feature boundary (`fit`) -- only those are scanned, counted and marked
-// "seen", exactly the k-mers a FASTA of the features holds; (2) the label planes of the unit; (3) one walk over the features
-// that overlap the unit: popcounts of the planes inside the feature -> counts[f][sg].
+// Feature mode (the consumers: map_feat_planes / map_feat_hits, sp_map.h).  The features lie back to back in one packed
+// sequence; a k-mer belongs to feature f iff it lies entirely inside [foff[f], foff[f + 1]).
 template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK, MAP_MIN_WAVES)
 k5_map_feat2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm,
@@ -719,46 +646,7 @@ k5_map_feat2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, c
              map_ptab ptab, const uint32_t *__restrict__ bloom, int bloom_bits,
              unsigned long long *__restrict__ counts) {
     MAP_UNIT_LDS_DECL(TABLE, 7);
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int k = kp.k;
-    auto span = [](int64_t a, int64_t b) -> unsigned long long {      // bits [a, b) of a unit, 0 <= a, b <= 64
-        if (b <= a) return 0ULL;
-        return (b >= 64 ? ~0ULL : ((1ULL << b) - 1ULL)) & ~((1ULL << a) - 1ULL);
-    };
-    for (; u < n_units; u += stride) {
-        const int64_t s0 = u * SP_UNIT;
-        int64_t lo = 0, hi = n_feat;           // the feature the unit starts in: last f with foff[f] <= s0
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (foff[mid] <= s0) lo = mid;
-            else hi = mid;
-        }
-        // (1) a boundary at `e` = foff[f + 1] disqualifies the starts (e - k, e): their k-mers run into the next feature
-        unsigned long long fit = ~0ULL;
-        for (int64_t f = lo; f < n_feat; f++) {
-            const int64_t e = foff[f + 1];
-            if (e - k + 1 >= s0 + SP_UNIT) break;
-            fit &= ~span((e - k + 1 > s0 ? e - k + 1 : s0) - s0, (e < s0 + SP_UNIT ? e : s0 + SP_UNIT) - s0);
-            if (e >= s0 + SP_UNIT) break;
-        }
-        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-        map_unit_scan64<TABLE>(pk, pm, nm, s0, kp, bloom, bloom_bits, ptab, lab, ulds, fit);
-        if (!(lab[0] | lab[1] | lab[2])) continue;
-        // (3) the features that overlap the unit (a start beyond the last feature's end is padding: never valid)
-        for (int64_t f = lo; f < n_feat; f++) {
-            const int64_t a = foff[f], e = foff[f + 1];
-            if (a >= s0 + SP_UNIT) break;
-            const unsigned long long within = span((a > s0 ? a : s0) - s0, (e < s0 + SP_UNIT ? e : s0 + SP_UNIT) - s0) & fit;
-            if (!((lab[0] | lab[1] | lab[2]) & within)) continue;
-            for (int sg = 0; sg < S; sg++) {
-                const int l = sg + 1;
-                const unsigned long long m = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) &
-                                             ((l & 4) ? lab[2] : ~lab[2]) & within;
-                if (m) atomicAdd(&counts[f * S + sg], (unsigned long long)__popcll(m));
-            }
-        }
-    }
+    map_feat_planes(map_walk_pair<TABLE>{pk, pm, nm, kp, ptab, bloom, bloom_bits}, ulds, kp.k, n_units, foff, n_feat, S, counts);
 }
 
 __global__ void __launch_bounds__(MAP_BLOCK)
@@ -766,22 +654,7 @@ k5_map_feat_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm
             int64_t n_units, const int64_t *__restrict__ foff, int64_t n_feat, int S,
             uint8_t *__restrict__ label, const uint32_t *__restrict__ bloom, int bloom_bits,
             unsigned long long *__restrict__ counts) {
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        map_feat_cursor cur;
-        cur.f = -1;
-        cur.next = 0;
-        map_pair_scan<uint32_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint32_t fwd, uint32_t rc) {
-            const uint32_t slot = sp_slot_of32(fwd, rc, kp);
-            const uint32_t l = label[slot];
-            if (l && map_feat_locate(cur, start, kp.k, foff, n_feat)) {
-                if (!(l & 0x80u)) label[slot] = (uint8_t)(l | 0x80u);
-                const int sg = (int)(l & 0x7fu) - 1;
-                atomicAdd(&counts[cur.f * S + sg], 1ULL);
-            }
-        });
-    }
+    map_feat_hits(map_walk_bytes{pk, nm, kp, label, bloom, bloom_bits}, kp.k, n_units, foff, n_feat, S, counts);
 }
 
 // ----------------------------------------------------------------- interval mode (BED features over the resident genome)
@@ -821,22 +694,7 @@ __global__ void __launch_bounds__(MAP_BLOCK)
 k5_map_mask_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams32 kp, int64_t n_units, int S,
                 uint8_t *__restrict__ label, const uint32_t *__restrict__ bloom, int bloom_bits,
                 const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks /* n_units x S */) {
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        const unsigned long long cv = cov[u];
-        if (__all(cv == 0ULL)) continue;         // nothing of this wave's 4096 starts lies in a feature
-        map_pair_scan<uint32_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint32_t fwd, uint32_t rc) {
-            const unsigned long long bit = 1ULL << (start & 63);
-            if (!(cv & bit)) return;
-            const uint32_t slot = sp_slot_of32(fwd, rc, kp);
-            const uint32_t l = label[slot];
-            if (l) {
-                if (!(l & 0x80u)) label[slot] = (uint8_t)(l | 0x80u);
-                atomicOr(&masks[u * S + ((int)(l & 0x7fu) - 1)], bit);
-            }
-        });
-    }
+    map_mask_hits(map_walk_bytes{pk, nm, kp, label, bloom, bloom_bits}, n_units, S, cov, masks);
 }
 
 __global__ void __launch_bounds__(256)
@@ -880,13 +738,6 @@ k4_count_seen(const uint8_t *__restrict__ label, int64_t nslots, unsigned long l
         for (int64_t i = (n16 << 4) + threadIdx.x; i < nslots; i += blockDim.x) n += (label[i] >> 7) & 1u;
     unsigned long long t = sp_block_sum_u64(n, red);
     if (threadIdx.x == 0 && t) atomicAdd(out, t);
-}
-
-static int64_t map_nslots_host(int64_t len, int64_t bin_size, int64_t chunk_size, int k) {
-    int64_t L = len > 0 ? len : 1;
-    int64_t nb = (L + bin_size - 1) / bin_size;
-    int64_t nch = chunk_size > 0 ? (L + (k - 1)) / chunk_size + 1 : 1;
-    return nb + nch;
 }
 
 // the flags of one sp_labels_set call -> page-locked host memory the kernel writes directly: a hipMemcpy of 32 bytes
@@ -965,48 +816,53 @@ int sp_map_filter_build(sp_ctx *ctx, const unsigned long long *d_keys, int64_t n
     return SP_OK;
 }
 
-// ----------------------------------------------------------------- one dispatch per walk mode
-// Each switches on the kind of table the label set lives in; the k > 15 kinds go on to sp_sparse.hip, beside their kernels.
-
-// bins mode, pair-table kinds: the descriptors of the queued chromosomes -> device, then the one launch
-static int map_bins_flush(sp_ctx *ctx, const std::vector<map_chrom_desc> &hd, int64_t n_ranges, const sp_map_params &P) {
-    if (n_ranges <= 0) return SP_OK;
-    int rcb = sp_buf_ensure(ctx, ctx->b_mapdesc, (int64_t)(hd.size() * sizeof(map_chrom_desc)));
-    if (rcb) return rcb;
-    // (pageable source: hipMemcpyAsync returns once the runtime has staged it, `hd` may die afterwards)
-    SP_HIP(ctx, hipMemcpyAsync(ctx->b_mapdesc.p, hd.data(), hd.size() * sizeof(map_chrom_desc), hipMemcpyHostToDevice,
-                              ctx->stream));
-    const sp_kparams32 kp = sp_make_kparams32(ctx->k);
-    const int64_t grid = map_grid(ctx, n_ranges);
-    const map_ptab T = map_ptab_of(ctx);
-    if (T.buckets)
-        SP_LAUNCH(ctx, "k5_map", k5_map2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
-                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
-    else
-        SP_LAUNCH(ctx, "k5_map", k5_map2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, (const map_chrom_desc *)ctx->b_mapdesc.p,
-                  (int)hd.size(), n_ranges, kp, P, T, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
-    return SP_OK;
+// ----------------------------------------------------------------- dispatch
+// The ONE place that turns the kind of a k <= 15 label table into its walker (map_planes_of<TABLE> / map_hits_of, sp_map.h):
+// `dense` is a mode's launcher, a generic lambda over the walker; the k > 15 kinds go on to `sparse`, the same mode's
+// launcher in sp_sparse.hip, beside their kernels.
+template <typename F, typename G>
+static int map_with_walker(sp_ctx *ctx, F &&dense, G &&sparse) {
+    switch (ctx->labels.kind) {
+    case SP_LABELS_COMPACT: return dense(map_planes_of<1>{});
+    case SP_LABELS_DIRECT: return dense(map_planes_of<0>{});
+    case SP_LABELS_LABEL_BYTES: return dense(map_hits_of{});
+    default: return sparse();
+    }
 }
 
-// bins mode, one chromosome: the pair-table kinds queue it in `hd` (every chromosome in ONE launch: map_bins_flush), the
+// bins mode, one chromosome: the planes walkers queue it in `hd` (every chromosome in ONE launch: map_bins_flush), the
 // other kinds launch here
 static int map_bins_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n,
                            std::vector<map_chrom_desc> &hd, int64_t &hd_ranges) {
     if (P.n_units == 0) return SP_OK;
     const int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    switch (ctx->labels.kind) {
-    case SP_LABELS_DIRECT:
-    case SP_LABELS_COMPACT:
-        hd.push_back(map_chrom_desc{c.d_pk, c.d_pm, c.d_nm, P.n_units, P.nslots, hd_ranges, d_counts, d_n});
-        hd_ranges += n_ranges;
+    return map_with_walker(ctx, [&](auto w) -> int {
+        if constexpr (decltype(w)::planes) {
+            hd.push_back(map_chrom_desc{c.d_pk, c.d_pm, c.d_nm, P.n_units, P.nslots, hd_ranges, d_counts, d_n});
+            hd_ranges += n_ranges;
+        } else {
+            SP_LAUNCH(ctx, "k5_map_lab", k5_map_lab, dim3((unsigned)map_grid(ctx, n_ranges)), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
+                      sp_make_kparams32(ctx->k), P, ctx->d_label, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+        }
         return SP_OK;
-    case SP_LABELS_LABEL_BYTES:
-        SP_LAUNCH(ctx, "k5_map_lab", k5_map_lab, dim3((unsigned)map_grid(ctx, n_ranges)), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
-                  sp_make_kparams32(ctx->k), P, ctx->d_label, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+    }, [&] { return sp_sparse_map_launch(ctx, c, P, d_counts, d_n); });
+}
+
+// the descriptors of the queued chromosomes -> device, then the one launch
+static int map_bins_flush(sp_ctx *ctx, const std::vector<map_chrom_desc> &hd, int64_t n_ranges, const sp_map_params &P) {
+    if (n_ranges <= 0) return SP_OK;      // (nothing queued: no planes walker, or no units)
+    int rcb = sp_buf_ensure(ctx, ctx->b_mapdesc, (int64_t)(hd.size() * sizeof(map_chrom_desc)));
+    if (rcb) return rcb;
+    // (pageable source: hipMemcpyAsync returns once the runtime has staged it, `hd` may die afterwards)
+    SP_HIP(ctx, hipMemcpyAsync(ctx->b_mapdesc.p, hd.data(), hd.size() * sizeof(map_chrom_desc), hipMemcpyHostToDevice,
+                              ctx->stream));
+    return map_with_walker(ctx, [&](auto w) -> int {
+        if constexpr (decltype(w)::planes)      // (only the planes walkers queue anything)
+            SP_LAUNCH(ctx, "k5_map", k5_map2<decltype(w)::table>, dim3((unsigned)map_grid(ctx, n_ranges)), dim3(MAP_BLOCK), 0,
+                      (const map_chrom_desc *)ctx->b_mapdesc.p, (int)hd.size(), n_ranges, sp_make_kparams32(ctx->k), P, map_ptab_of(ctx),
+                      (const uint32_t *)ctx->d_bloom, ctx->bloom_bits);
         return SP_OK;
-    default:
-        return sp_sparse_map_launch(ctx, c, P, d_counts, d_n);
-    }
+    }, [] { return SP_OK; });
 }
 
 // feature mode: one packed sequence of features
@@ -1014,22 +870,15 @@ static int map_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_
                            const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts) {
     const sp_kparams32 kp = sp_make_kparams32(ctx->k);
     const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
-    switch (ctx->labels.kind) {
-    case SP_LABELS_COMPACT:
-        SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm, kp, n_units,
-                  d_foff, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
+    return map_with_walker(ctx, [&](auto w) -> int {
+        if constexpr (decltype(w)::planes)
+            SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<decltype(w)::table>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
+                      kp, n_units, d_foff, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
+        else
+            SP_LAUNCH(ctx, "k5_map_feat_lab", k5_map_feat_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp, n_units,
+                      d_foff, n_feat, S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
         return SP_OK;
-    case SP_LABELS_DIRECT:
-        SP_LAUNCH(ctx, "k5_map_feat", k5_map_feat2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm, kp, n_units,
-                  d_foff, n_feat, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
-        return SP_OK;
-    case SP_LABELS_LABEL_BYTES:
-        SP_LAUNCH(ctx, "k5_map_feat_lab", k5_map_feat_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp, n_units,
-                  d_foff, n_feat, S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_counts);
-        return SP_OK;
-    default:
-        return sp_sparse_feat_launch(ctx, d_pk, d_pm, d_nm, n_units, d_foff, n_feat, S, d_counts);
-    }
+    }, [&] { return sp_sparse_feat_launch(ctx, d_pk, d_pm, d_nm, n_units, d_foff, n_feat, S, d_counts); });
 }
 
 // interval mode: the per-unit subgenome masks of one chromosome
@@ -1037,22 +886,15 @@ static int map_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, con
                            unsigned long long *d_masks) {
     const sp_kparams32 kp = sp_make_kparams32(ctx->k);
     const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
-    switch (ctx->labels.kind) {
-    case SP_LABELS_COMPACT:
-        SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp,
-                  n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+    return map_with_walker(ctx, [&](auto w) -> int {
+        if constexpr (decltype(w)::planes)
+            SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<decltype(w)::table>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
+                      c.d_nm, kp, n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        else
+            SP_LAUNCH(ctx, "k5_map_mask_lab", k5_map_mask_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, n_units,
+                      S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
         return SP_OK;
-    case SP_LABELS_DIRECT:
-        SP_LAUNCH(ctx, "k5_map_mask", k5_map_mask2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp,
-                  n_units, S, map_ptab_of(ctx), (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-        return SP_OK;
-    case SP_LABELS_LABEL_BYTES:
-        SP_LAUNCH(ctx, "k5_map_mask_lab", k5_map_mask_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, n_units,
-                  S, ctx->d_label, (const uint32_t *)ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-        return SP_OK;
-    default:
-        return sp_sparse_mask_launch(ctx, c, n_units, S, d_cov, d_masks);
-    }
+    }, [&] { return sp_sparse_mask_launch(ctx, c, n_units, S, d_cov, d_masks); });
 }
 
 // the labelled k-mers a walk has marked "seen"

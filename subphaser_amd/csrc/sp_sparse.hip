@@ -6,7 +6,9 @@
 //            -> radix sort -> run-length encode -> keep count >= lower_count   (per chromosome), and the dump
 //   labels : labelled k-mers in an open-addressing hash table, the pair-keyed table and the quad-bucket table
 //            (+ the L2-resident pre-filter)
-//   map    : the k > 15 map, feature and mask kernels: same binning code path as the dense engine
+//   map    : the k > 15 walkers (sps_walk_pair: map_unit_scan64_h; sps_walk_kmer: sps_lookup) and the six kernels that pair them
+//            with the consumers of sp_map.h: k5_map_sparse2, k5_map_feat_sparse2, k5_map_mask_sparse2 (planes) and
+//            k5_map_sparse_lab, k5_map_feat_sparse_lab, k5_map_mask_sparse_lab (hits); one dispatch (sps_with_walker)
 //   lists  : the multi-GPU exports of the per-chromosome lists (sp_sparse_sizes / _sample / _split / _export / _view)
 //
 // The sort and the run-length encode are rocPRIM device primitives (plain library ops on this secondary path);
@@ -201,9 +203,30 @@ sps_pair_seen(const unsigned long long *__restrict__ keys, int64_t n, int k, con
     if (threadIdx.x == 0 && t) atomicAdd(out, t);
 }
 
-// K5 for k > 15, per-k-mer table (SP_LABELS_KMER_HASH: more than 7 subgenomes, or on demand -- sp_labelplan.h): the rolling scan, one filter probe per pair
-// of starts, one 16-byte look-up per candidate start.  (The pair-keyed table takes k5_map_sparse2 below; the unrolled
-// pair kernel of rounds 1-4 -- 532 KB of machine code -- was removed in round 6.)
+// The hits walker of k > 15 (sp_map.h), per-k-mer table (SP_LABELS_KMER_HASH: more than 7 subgenomes, or on demand --
+// sp_labelplan.h): the rolling scan, one filter probe per pair of starts, one 16-byte look-up per candidate start.
+// sps_lookup marks "seen" as it finds, so `counted` is asked before the look-up.  (`kp` refers to the kernel's argument:
+// a walker lives inside one kernel's frame.)
+struct sps_walk_kmer {
+    const uint32_t *pk, *nm;
+    const sp_kparams &kp;
+    unsigned long long *htab;
+    uint64_t mask;
+    const uint32_t *bloom;
+    int nbits;
+    template <typename F>
+    __device__ __forceinline__ void scan(int64_t s0, F &&each) const {
+        map_pair_scan<uint64_t>(pk, nm, s0, kp, bloom, nbits,
+                                [&](int64_t start, uint64_t fwd, uint64_t rc) { each(start, fwd < rc ? fwd : rc); });
+    }
+    template <typename C>
+    __device__ __forceinline__ int look(uint64_t key, C &&counted) const {
+        return counted() ? sps_lookup(key, htab, mask) : -1;
+    }
+};
+
+// K5 for k > 15 on that walker: bins, then features and intervals.  (The pair-keyed tables take k5_map_sparse2 below; the
+// unrolled pair kernel of rounds 1-4 -- 532 KB of machine code -- was removed in round 6.)
 __global__ void __launch_bounds__(MAP_BLOCK)
 k5_map_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams kp, sp_map_params P,
                   unsigned long long *__restrict__ htab, uint64_t mask,
@@ -211,41 +234,22 @@ k5_map_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ 
                   unsigned long long *__restrict__ n_mapped) {
     __shared__ int hist[MAP_LDS_ENTRIES];
     __shared__ unsigned long long red[16];
-    unsigned long long mapped = 0;
-    const int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    for (int64_t r = blockIdx.x; r < n_ranges; r += gridDim.x) {
-        const int64_t u = r * MAP_BLOCK + threadIdx.x;
-        const int64_t slot_lo = map_slot(r * MAP_RANGE, P, kp.k);
-        if (P.use_lds) {
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) hist[i] = 0;
-            __syncthreads();
-        }
-        if (u < P.n_units) {
-            map_pair_scan<uint64_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint64_t fwd, uint64_t rc) {
-                const int sg = sps_lookup(fwd < rc ? fwd : rc, htab, mask);
-                if (sg < 0) return;
-                const int64_t os = map_slot(start, P, kp.k);
-                if (P.use_lds)
-                    atomicAdd(&hist[(os - slot_lo) * P.S + sg], 1);
-                else if (os < P.nslots)
-                    atomicAdd(&slot_counts[os * P.S + sg], 1);
-                mapped++;
-            });
-        }
-        if (P.use_lds) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) {
-                int v = hist[i];
-                if (v) {
-                    int64_t os = slot_lo + i / P.S;
-                    if (os < P.nslots) atomicAdd(&slot_counts[os * P.S + (i % P.S)], v);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    unsigned long long t = sp_block_sum_u64(mapped, red);
-    if (threadIdx.x == 0 && t) atomicAdd(n_mapped, t);
+    const sps_walk_kmer walk{pk, nm, kp, htab, mask, bloom, bloom_bits};
+    map_bins_acc acc(hist, P, kp.k);
+    map_bins_chrom(acc, red, slot_counts, n_mapped, [&](int64_t s0) { acc.add_hits(walk, s0); });
+}
+__global__ void __launch_bounds__(MAP_BLOCK)
+k5_map_feat_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams kp, int64_t n_units,
+                       const int64_t *__restrict__ foff, int64_t n_feat, int S,
+                       unsigned long long *__restrict__ htab, uint64_t mask,
+                       const uint32_t *__restrict__ bloom, int bloom_bits, unsigned long long *__restrict__ counts) {
+    map_feat_hits(sps_walk_kmer{pk, nm, kp, htab, mask, bloom, bloom_bits}, kp.k, n_units, foff, n_feat, S, counts);
+}
+__global__ void __launch_bounds__(MAP_BLOCK)
+k5_map_mask_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams kp, int64_t n_units, int S,
+                       unsigned long long *__restrict__ htab, uint64_t mask, const uint32_t *__restrict__ bloom, int bloom_bits,
+                       const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks) {
+    map_mask_hits(sps_walk_kmer{pk, nm, kp, htab, mask, bloom, bloom_bits}, n_units, S, cov, masks);
 }
 
 // ------------------------------------------------------------------ quad-bucket label table for k > 15 (round 6)
@@ -621,7 +625,26 @@ __device__ __forceinline__ void map_unit_scan64_h(const uint32_t *__restrict__ p
     for (int bit = 0; bit < NP; bit++) lab[bit] = U.planes[bit * MAP_BLOCK + tid];
 }
 
-// (six waves per SIMD = TWO 768-thread workgroups per CU: at 82 VGPRs -- one more than that allows -- the kernel ran one: 52.6 -> 66.6 ms)
+// the planes walker of k > 15 (sp_map.h): the two-phase walk over the pair-keyed hash table (TABLE 0) or the quad buckets (1)
+// (`kp` and `T` refer to the kernel's arguments: a walker lives inside one kernel's frame)
+template <int TABLE>
+struct sps_walk_pair {
+    const uint32_t *pk, *pm, *nm;
+    const sp_kparams &kp;
+    unsigned long long *htab;
+    uint64_t hmask;
+    const sq_tab &T;
+    const uint32_t *bloom;
+    int nbits;
+    __device__ __forceinline__ void operator()(int64_t s0, unsigned long long lab[3], const map_unit_lds &U,
+                                               unsigned long long cm = ~0ULL) const {
+        map_unit_scan64_h<TABLE>(pk, pm, nm, s0, kp, bloom, nbits, htab, hmask, T, lab, U, cm);
+    }
+};
+
+// (the bound: six waves per SIMD, that is three workgroups of MAP_BLOCK = 512 threads per CU, leave a wave 80 VGPRs, and the
+// walk needs every one of them.  What a register too many costs was measured in round 6, with workgroups of 768: at 82 VGPRs
+// the kernel ran one workgroup per CU instead of two, 52.6 -> 66.6 ms)
 template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK, 6)
 k5_map_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm, sp_kparams kp,
@@ -630,67 +653,15 @@ k5_map_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm,
     __shared__ int hist[MAP_LDS_ENTRIES];
     __shared__ unsigned long long red[16];
     MAP_UNIT_LDS_DECL(TABLE, 8);
-    unsigned long long mapped = 0;
-    const int64_t n_ranges = (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK;
-    for (int64_t r = blockIdx.x; r < n_ranges; r += gridDim.x) {
-        const int64_t u = r * MAP_BLOCK + threadIdx.x;
-        // the range's first output slot and where it ends (uniform; once per range, not per hit)
-        const int64_t slot_lo = map_slot(r * MAP_RANGE, P, kp.k), end_lo = map_slot_end(r * MAP_RANGE, P, kp.k);
-        const bool one_slot = end_lo >= (r + 1) * MAP_RANGE;
-        if (P.use_lds) {
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) hist[i] = 0;
-            __syncthreads();
-        }
-        if (u < P.n_units) {
-            unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-            map_unit_scan64_h<TABLE>(pk, pm, nm, u * SP_UNIT, kp, bloom, bloom_bits, htab, hmask, T, lab, ulds);
-            if (lab[0] | lab[1] | lab[2]) {
-                auto add = [&](int64_t os, unsigned long long within) {
-                    for (int sg = 0; sg < P.S; sg++) {
-                        const int l = sg + 1;
-                        const unsigned long long m = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) &
-                                                     ((l & 4) ? lab[2] : ~lab[2]) & within;
-                        const int v = __popcll(m);
-                        if (!v) continue;
-                        if (P.use_lds) atomicAdd(&hist[(int)(os - slot_lo) * P.S + sg], v);
-                        else if (os < P.nslots) atomicAdd(&slot_counts[os * P.S + sg], v);
-                        mapped += v;
-                    }
-                };
-                const int64_t s0 = u * SP_UNIT;
-                if (one_slot) {
-                    add(slot_lo, ~0ULL);
-                } else {
-                    int64_t p = s0;
-                    while (p < s0 + SP_UNIT) {
-                        int64_t e = map_slot_end(p, P, kp.k);
-                        if (e > s0 + SP_UNIT) e = s0 + SP_UNIT;
-                        const int a = (int)(p - s0), b = (int)(e - s0);
-                        const unsigned long long within = (b >= 64 ? ~0ULL : ((1ULL << b) - 1ULL)) & ~((1ULL << a) - 1ULL);
-                        if ((lab[0] | lab[1] | lab[2]) & within) add(map_slot(p, P, kp.k), within);
-                        p = e;
-                    }
-                }
-            }
-        }
-        if (P.use_lds) {
-            __syncthreads();
-            for (int i = threadIdx.x; i < MAP_LDS_ENTRIES; i += MAP_BLOCK) {
-                int v = hist[i];
-                if (v) {
-                    int64_t os = slot_lo + i / P.S;
-                    if (os < P.nslots) atomicAdd(&slot_counts[os * P.S + (i % P.S)], v);
-                }
-            }
-            __syncthreads();
-        }
-    }
-    unsigned long long t = sp_block_sum_u64(mapped, red);
-    if (threadIdx.x == 0 && t) atomicAdd(n_mapped, t);
+    const sps_walk_pair<TABLE> walk{pk, pm, nm, kp, htab, hmask, T, bloom, bloom_bits};
+    map_bins_acc acc(hist, P, kp.k);
+    map_bins_chrom(acc, red, slot_counts, n_mapped, [&](int64_t s0) {
+        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
+        walk(s0, lab, ulds);
+        acc.add_planes(s0, lab);
+    });
 }
-
-// feature mode (sp_map.hip: k5_map_feat2), pair-keyed table: the rolled walk over the starts whose k-mer crosses no feature
-// boundary, then popcounts of the label planes per overlapping feature
+// feature mode and interval mode on the same walker (the consumers: sp_map.h)
 template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK)
 k5_map_feat_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm, sp_kparams kp,
@@ -698,64 +669,16 @@ k5_map_feat_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict_
                     unsigned long long *__restrict__ htab, uint64_t hmask, sq_tab T,
                     const uint32_t *__restrict__ bloom, int bloom_bits, unsigned long long *__restrict__ counts) {
     MAP_UNIT_LDS_DECL(TABLE, 8);
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    const int k = kp.k;
-    auto span = [](int64_t a, int64_t b) -> unsigned long long {      // bits [a, b) of a unit, 0 <= a, b <= 64
-        if (b <= a) return 0ULL;
-        return (b >= 64 ? ~0ULL : ((1ULL << b) - 1ULL)) & ~((1ULL << a) - 1ULL);
-    };
-    for (; u < n_units; u += stride) {
-        const int64_t s0 = u * SP_UNIT;
-        int64_t lo = 0, hi = n_feat;           // the feature the unit starts in: last f with foff[f] <= s0
-        while (hi - lo > 1) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (foff[mid] <= s0) lo = mid;
-            else hi = mid;
-        }
-        unsigned long long fit = ~0ULL;        // a boundary at e = foff[f + 1] disqualifies the starts (e - k, e)
-        for (int64_t f = lo; f < n_feat; f++) {
-            const int64_t e = foff[f + 1];
-            if (e - k + 1 >= s0 + SP_UNIT) break;
-            fit &= ~span((e - k + 1 > s0 ? e - k + 1 : s0) - s0, (e < s0 + SP_UNIT ? e : s0 + SP_UNIT) - s0);
-            if (e >= s0 + SP_UNIT) break;
-        }
-        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-        map_unit_scan64_h<TABLE>(pk, pm, nm, s0, kp, bloom, bloom_bits, htab, hmask, T, lab, ulds, fit);
-        if (!(lab[0] | lab[1] | lab[2])) continue;
-        for (int64_t f = lo; f < n_feat; f++) {
-            const int64_t a = foff[f], e = foff[f + 1];
-            if (a >= s0 + SP_UNIT) break;
-            const unsigned long long within = span((a > s0 ? a : s0) - s0, (e < s0 + SP_UNIT ? e : s0 + SP_UNIT) - s0) & fit;
-            if (!((lab[0] | lab[1] | lab[2]) & within)) continue;
-            for (int sg = 0; sg < S; sg++) {
-                const int l = sg + 1;
-                const unsigned long long m = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) &
-                                             ((l & 4) ? lab[2] : ~lab[2]) & within;
-                if (m) atomicAdd(&counts[f * S + sg], (unsigned long long)__popcll(m));
-            }
-        }
-    }
+    map_feat_planes(sps_walk_pair<TABLE>{pk, pm, nm, kp, htab, hmask, T, bloom, bloom_bits}, ulds, kp.k, n_units, foff, n_feat, S,
+                    counts);
 }
-// the same for the per-k-mer table (more than 7 subgenomes): the rolling scan, one look-up per candidate start
+template <int TABLE>
 __global__ void __launch_bounds__(MAP_BLOCK)
-k5_map_feat_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams kp, int64_t n_units,
-                       const int64_t *__restrict__ foff, int64_t n_feat, int S,
-                       unsigned long long *__restrict__ htab, uint64_t mask,
-                       const uint32_t *__restrict__ bloom, int bloom_bits, unsigned long long *__restrict__ counts) {
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        map_feat_cursor cur;
-        cur.f = -1;
-        cur.next = 0;
-        map_pair_scan<uint64_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint64_t fwd, uint64_t rc) {
-            if (!map_feat_locate(cur, start, kp.k, foff, n_feat)) return;   // runs into the next feature
-            const int sg = sps_lookup(fwd < rc ? fwd : rc, htab, mask);
-            if (sg < 0) return;
-            atomicAdd(&counts[cur.f * S + sg], 1ULL);
-        });
-    }
+k5_map_mask_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm, sp_kparams kp,
+                    int64_t n_units, int S, unsigned long long *__restrict__ htab, uint64_t hmask, sq_tab T, const uint32_t *__restrict__ bloom,
+                    int bloom_bits, const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks) {
+    MAP_UNIT_LDS_DECL(TABLE, 8);
+    map_mask_planes(sps_walk_pair<TABLE>{pk, pm, nm, kp, htab, hmask, T, bloom, bloom_bits}, ulds, n_units, S, cov, masks);
 }
 
 __global__ void __launch_bounds__(256)
@@ -985,110 +908,64 @@ int sp_sparse_labels_build(sp_ctx *ctx, const sp_label_plan &plan, const unsigne
     }
 }
 
-// The k > 15 half of the four dispatches of sp_map.hip: SP_LABELS_QUAD, SP_LABELS_PAIR_HASH, else SP_LABELS_KMER_HASH
+// The ONE place that turns the kind of a k > 15 label table into its walker (sp_map.h): `launch` is a mode's launcher, a
+// generic lambda over the walker that is also handed the hash table every k > 15 kernel takes.
+template <typename F>
+static int sps_with_walker(sp_ctx *ctx, F &&launch) {
+    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
+    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
+    switch (ctx->labels.kind) {
+    case SP_LABELS_QUAD: return launch(map_planes_of<1>{}, htab, hmask);
+    case SP_LABELS_PAIR_HASH: return launch(map_planes_of<0>{}, htab, hmask);
+    default: return launch(map_hits_of{}, htab, hmask);      // SP_LABELS_KMER_HASH
+    }
+}
+
+// the k > 15 halves of the three mode launchers of sp_map.hip.  Bins: one launch per chromosome.
 int sp_sparse_map_launch(sp_ctx *ctx, sp_chrom &c, const sp_map_params &P, int *d_counts, unsigned long long *d_n) {
     if (P.n_units == 0) return SP_OK;
     const sp_kparams kp = sp_make_kparams(ctx->k);
     const int64_t grid = map_grid(ctx, (P.n_units + MAP_BLOCK - 1) / MAP_BLOCK);
-    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
-    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
-    switch (ctx->labels.kind) {
-    case SP_LABELS_QUAD:
-        SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
-                  htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+    return sps_with_walker(ctx, [&](auto w, unsigned long long *htab, uint64_t hmask) -> int {
+        if constexpr (decltype(w)::planes)
+            SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<decltype(w)::table>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
+                      c.d_nm, kp, P, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
+        else
+            SP_LAUNCH(ctx, "k5_map_sparse_lab", k5_map_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
+                      htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
         return SP_OK;
-    case SP_LABELS_PAIR_HASH:
-        SP_LAUNCH(ctx, "k5_map_sparse", k5_map_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm, c.d_nm, kp, P,
-                  htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
-        return SP_OK;
-    default:
-        SP_LAUNCH(ctx, "k5_map_sparse_lab", k5_map_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm, kp, P,
-                  htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts, d_n);
-        return SP_OK;
-    }
+    });
 }
 
 int sp_sparse_feat_launch(sp_ctx *ctx, const uint32_t *d_pk, const uint32_t *d_pm, const uint32_t *d_nm, int64_t n_units,
                           const int64_t *d_foff, int64_t n_feat, int S, unsigned long long *d_counts) {
     const sp_kparams kp = sp_make_kparams(ctx->k);
     const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
-    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
-    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
-    switch (ctx->labels.kind) {
-    case SP_LABELS_QUAD:
-        SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
-                  kp, n_units, d_foff, n_feat, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts);
+    return sps_with_walker(ctx, [&](auto w, unsigned long long *htab, uint64_t hmask) -> int {
+        if constexpr (decltype(w)::planes)
+            SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<decltype(w)::table>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk,
+                      d_pm, d_nm, kp, n_units, d_foff, n_feat, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts);
+        else
+            SP_LAUNCH(ctx, "k5_map_feat_sparse_lab", k5_map_feat_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp,
+                      n_units, d_foff, n_feat, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts);
         return SP_OK;
-    case SP_LABELS_PAIR_HASH:
-        SP_LAUNCH(ctx, "k5_map_feat_sparse", k5_map_feat_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_pm, d_nm,
-                  kp, n_units, d_foff, n_feat, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_counts);
-        return SP_OK;
-    default:
-        SP_LAUNCH(ctx, "k5_map_feat_sparse_lab", k5_map_feat_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, d_pk, d_nm, kp,
-                  n_units, d_foff, n_feat, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_counts);
-        return SP_OK;
-    }
+    });
 }
 
 // interval mode (sp_map.hip: kv_cover / kv_count): the k > 15 scan that fills the per-unit subgenome masks
-__global__ void __launch_bounds__(MAP_BLOCK)
-k5_map_mask_sparse_lab(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ nm, sp_kparams kp, int64_t n_units, int S,
-                       unsigned long long *__restrict__ htab, uint64_t mask, const uint32_t *__restrict__ bloom, int bloom_bits,
-                       const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks) {
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        const unsigned long long cv = cov[u];
-        if (__all(cv == 0ULL)) continue;
-        map_pair_scan<uint64_t>(pk, nm, u * SP_UNIT, kp, bloom, bloom_bits, [&](int64_t start, uint64_t fwd, uint64_t rc) {
-            const unsigned long long bit = 1ULL << (start & 63);
-            if (!(cv & bit)) return;
-            const int sg = sps_lookup(fwd < rc ? fwd : rc, htab, mask);
-            if (sg >= 0) atomicOr(&masks[u * S + sg], bit);
-        });
-    }
-}
-
-template <int TABLE>
-__global__ void __launch_bounds__(MAP_BLOCK)
-k5_map_mask_sparse2(const uint32_t *__restrict__ pk, const uint32_t *__restrict__ pm, const uint32_t *__restrict__ nm, sp_kparams kp,
-                    int64_t n_units, int S, unsigned long long *__restrict__ htab, uint64_t hmask, sq_tab T, const uint32_t *__restrict__ bloom,
-                    int bloom_bits, const unsigned long long *__restrict__ cov, unsigned long long *__restrict__ masks) {
-    MAP_UNIT_LDS_DECL(TABLE, 8);
-    int64_t u = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-    for (; u < n_units; u += stride) {
-        const unsigned long long cv = cov[u];
-        if (__all(cv == 0ULL)) continue;
-        unsigned long long lab[3] = {0ULL, 0ULL, 0ULL};
-        map_unit_scan64_h<TABLE>(pk, pm, nm, u * SP_UNIT, kp, bloom, bloom_bits, htab, hmask, T, lab, ulds, cv);
-        for (int sg = 0; sg < S; sg++) {
-            const int l = sg + 1;
-            masks[u * S + sg] = ((l & 1) ? lab[0] : ~lab[0]) & ((l & 2) ? lab[1] : ~lab[1]) & ((l & 4) ? lab[2] : ~lab[2]) & cv;
-        }
-    }
-}
-
 int sp_sparse_mask_launch(sp_ctx *ctx, sp_chrom &c, int64_t n_units, int S, const unsigned long long *d_cov,
                           unsigned long long *d_masks) {
     const sp_kparams kp = sp_make_kparams(ctx->k);
     const int64_t grid = map_grid(ctx, (n_units + MAP_BLOCK - 1) / MAP_BLOCK);
-    unsigned long long *htab = (unsigned long long *)ctx->d_hkeys;
-    const uint64_t hmask = (uint64_t)(ctx->hcap - 1);
-    switch (ctx->labels.kind) {
-    case SP_LABELS_QUAD:
-        SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<1>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
-                  c.d_nm, kp, n_units, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+    return sps_with_walker(ctx, [&](auto w, unsigned long long *htab, uint64_t hmask) -> int {
+        if constexpr (decltype(w)::planes)
+            SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<decltype(w)::table>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0,
+                      c.d_pk, c.d_pm, c.d_nm, kp, n_units, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
+        else
+            SP_LAUNCH(ctx, "k5_map_mask_sparse_lab", k5_map_mask_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
+                      kp, n_units, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
         return SP_OK;
-    case SP_LABELS_PAIR_HASH:
-        SP_LAUNCH(ctx, "k5_map_mask_sparse", k5_map_mask_sparse2<0>, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_pm,
-                  c.d_nm, kp, n_units, S, htab, hmask, sq_tab_of(ctx), ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-        return SP_OK;
-    default:
-        SP_LAUNCH(ctx, "k5_map_mask_sparse_lab", k5_map_mask_sparse_lab, dim3((unsigned)grid), dim3(MAP_BLOCK), 0, c.d_pk, c.d_nm,
-                  kp, n_units, S, htab, hmask, ctx->d_bloom, ctx->bloom_bits, d_cov, d_masks);
-        return SP_OK;
-    }
+    });
 }
 
 int sp_sparse_hit(sp_ctx *ctx, unsigned long long *d_n) {

@@ -14,8 +14,8 @@ from test_gpu_map_runs import _keys_by_position
 _B = np.frombuffer(b"ACGT", dtype=np.uint8)
 SEG_LEN = 160
 UNIT = 64
-MAP_RANGE = 32768            # starts per workgroup pass of the bins walk (MAP_BLOCK x SP_UNIT, csrc/sp_map.h)
-MAP_LDS_ENTRIES = 1024       # its LDS histogram (csrc/sp_map.h)
+MAP_RANGE = 32768            # starts per workgroup pass of the bins walk (MAP_BLOCK x SP_UNIT, csrc/sp_mapslots.h)
+MAP_LDS_ENTRIES = 1024       # its LDS histogram (csrc/sp_mapslots.h)
 
 
 def lengths(k):
