@@ -511,6 +511,45 @@ int sp_nj_set_guard(sp_ctx *ctx, int64_t limit);
 int sp_dom_search(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int P,
                   const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry, int32_t *out);
 
+/* ---- LTR-RT domain trees: profile alignment with traceback, peptides, pairwise comparison of aligned rows ------
+ * The alignment is defined by integer arithmetic (csrc/sp_domalign.h holds the definition: the item, the back-pointer
+ * order of the three cells, the trace, the outputs, the limits); it is the Viterbi path of sp_dom_search's local search
+ * over a window of one frame, residues placed on the match nodes of one profile, and is not mafft or hmmalign.  Inserted
+ * residues appear in no column.
+ *   sp_dom_align     n items: interval [start[q], end[q]) of chromosome chrom[q] (as sp_dom_search takes them), frame[q]
+ *                    (0..5), the residue window [i0[q], i1[q]] of that frame (0-based, inclusive, at most 8192 residues),
+ *                    profile prof[q] of the P profiles (tables as sp_dom_search takes them; they go up once per call).
+ *                    hit: n x 5 int32 = score, i_start, i_end, k_start, k_end (i indices of the FRAME, k 1-based, both
+ *                    inclusive).  col: int32 at coff[q] .., coff[q + 1] - coff[q] = the nodes of profile prof[q] (coff[0]
+ *                    = 0): the frame index of the residue in node k's match state, -1 for a node the path deletes or
+ *                    does not reach.  Caller-owned host memory.  The items go in batches whose back-pointer planes (a
+ *                    byte per cell) fit 1 GiB, a batch's items longest first; a batch is two or three launches: the fill
+ *                    (one wave per item) and the trace.  n = 0 is fine.
+ *   sp_dom_align_set_batch  the most items a batch takes (0 = the default: by the 1 GiB cap); tests use 1 and 3 -- no
+ *                    result depends on it
+ *   sp_dom_peptide   the residue codes of the windows of n items (0..19 = A C D E F G H I K L M N P Q R S T V W Y, 20 = a
+ *                    codon with an invalid base, 21 = a stop codon): pep uint8 at poff[q] .., poff[q + 1] - poff[q] =
+ *                    i1[q] - i0[q] + 1 (poff[0] = 0).  n = 0 is fine.
+ *   sp_aln_pairs     N rows of C bytes in host memory: 0..19 are residues, anything else (20, 21, the gap 255) is "no
+ *                    residue".  both[a][b] = the columns where both rows hold a residue, same[a][b] = those where the two
+ *                    are equal.  Both N x N int32, written in full: symmetric, the diagonal is (own count, own count).
+ *                    2 <= N <= 4096, 1 <= C <= 8192.  A workgroup owns a tile of 32 x 32 pairs and stages its rows in
+ *                    LDS 1024 columns at a time (66048 bytes).
+ * SP_EINVAL: a NULL pointer; no genome; a chromosome out of range; an interval off its chromosome or with end < start;
+ * a frame outside 0..5; i0 < 0 or i0 > i1; i1 beyond the frame's residues; prof outside 0..P-1; P < 1; node offsets that
+ * do not ascend from 0; coff / poff that do not start at 0 or do not leave an item its nodes / its window; a score
+ * outside its range (as sp_dom_search); N < 2 or C < 1; a batch size below 0 -- all checked on the host before any
+ * launch.  SP_EUNSUP: a window above 8192 residues, M > 2048, P > 4096, an interval above 65536 bases, N > 4096,
+ * C > 8192 -- decided before any allocation.  SP_ENOMEM: the workspace does not fit (the message has its size).          */
+int sp_dom_align(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end,
+                 const int32_t *frame, const int32_t *i0, const int32_t *i1, const int32_t *prof, int P,
+                 const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry, int32_t *hit,
+                 const int64_t *coff, int32_t *col);
+int sp_dom_align_set_batch(sp_ctx *ctx, int64_t items);
+int sp_dom_peptide(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end,
+                   const int32_t *frame, const int32_t *i0, const int32_t *i1, const int64_t *poff, uint8_t *pep);
+int sp_aln_pairs(sp_ctx *ctx, int N, int C, const uint8_t *rows, int32_t *same, int32_t *both);
+
 /* ---- profiling: per-kernel HIP-event timing on the context's stream ------ */
 int sp_prof_enable(sp_ctx *ctx, int on);
 int sp_prof_reset(sp_ctx *ctx);

@@ -29,6 +29,10 @@ DOMAINS_MAX_M, DOMAINS_MAX_LEN, DOMAINS_MAX_P = 2048, 65536, 4096   # SP_DM_MAXM
 DOMAINS_MAX_ENTRIES = 1 << 24                      # (element, profile) entries of one sp_dom_search call
 DOMAINS_CALL_ENTRIES = 1 << 20                     # entries Context.dom_search puts in one call: the library lists and sorts six
                                                    # items of 24 bytes per entry on the host, 150 MB at this size (2.4 GB at the limit)
+DOMALIGN_MAX_WIN = 8192                            # SP_DA_MAXWIN in csrc/sp_domalign.h
+ALN_PAIRS_MAX_N, ALN_PAIRS_MAX_C = 4096, 8192      # SP_DA_MAXN, SP_DA_MAXC in csrc/sp_domalign.h
+ALN_GAP = 255                                      # SP_DA_GAP: "no residue" in the rows of aln_pairs (as is every byte above 19)
+PEPTIDE_LETTERS = "ACDEFGHIKLMNPQRSTVWYX*"         # the residue codes 0..21 of dom_peptide
 WILCOXON_MAX_GROUP = 64                            # SP_WX_MAXG in csrc/sp_wilcoxon.h
 
 # every symbol include/subphaser_hip.h declares (checked by tests/test_abi.py)
@@ -43,6 +47,7 @@ SYMBOLS = [
     "sp_ltr_align", "sp_ltr_seeds", "sp_ltr_hsps", "sp_ltr_detect_set_chunk", "sp_ltr_detect_set_capacity",
     "sp_ltr_sketch", "sp_ltr_sketch_set_chunk", "sp_ltr_sketch_pairs", "sp_nj_tree", "sp_nj_set_mode", "sp_nj_set_guard",
     "sp_dom_search",
+    "sp_dom_align", "sp_dom_align_set_batch", "sp_dom_peptide", "sp_aln_pairs",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
     "sp_synth_chrom", "sp_synth_chrom_range", "sp_host_alloc", "sp_host_free", "sp_host_register", "sp_host_unregister", "sp_dev_alloc", "sp_dev_free", "sp_dev_copy_to_host", "sp_dev_copy_from_host",
@@ -151,6 +156,10 @@ def load():
     L.sp_ltr_sketch.argtypes = [vp, i64, vp, vp, vp, ci, ci, vp, vp]
     L.sp_ltr_sketch_set_chunk.argtypes = [vp, ci]
     L.sp_dom_search.argtypes = [vp, i64, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.sp_dom_align.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
+    L.sp_dom_align_set_batch.argtypes = [vp, i64]
+    L.sp_dom_peptide.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.sp_aln_pairs.argtypes = [vp, ci, ci, vp, vp, vp]
     L.sp_ltr_sketch_pairs.argtypes = [vp, ci, ci, vp, vp, vp, vp]
     L.sp_nj_tree.argtypes = [vp, vp, ci, vp]
     L.sp_nj_set_mode.argtypes = [vp, ci]
@@ -1073,6 +1082,64 @@ class Context:
             self._ck(self.L.sp_dom_search(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans),
                                           _p(entry), _p(out[a:b])))
         return out
+
+    # -------------------------------------------------------------- LTR domain trees
+    @staticmethod
+    def _items(chrom, start, end, frame, i0, i1):
+        chrom, frame = np.ascontiguousarray(chrom, np.int32), np.ascontiguousarray(frame, np.int32)
+        start, end = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
+        i0, i1 = np.ascontiguousarray(i0, np.int32), np.ascontiguousarray(i1, np.int32)
+        n = int(chrom.size)
+        if not all(a.size == n for a in (start, end, frame, i0, i1)):
+            raise ValueError("chrom, start, end, frame, i0 and i1 must have one entry per item")
+        return n, chrom, start, end, frame, i0, i1
+
+    def dom_align(self, chrom, start, end, frame, i0, i1, prof, moff, emis, trans, entry):
+        """The Viterbi path of the residue windows [i0, i1] (inclusive, of frame `frame` of the interval [start, end)) on
+        profile `prof` (sp_dom_align; definition in csrc/sp_domalign.h): (hit int32 [n, 5] = score, i_start, i_end,
+        k_start, k_end; col int32, flat; coff int64 [n + 1]) -- col[coff[q] + k - 1] is the frame index of the residue on
+        node k of item q's profile, -1 where the path has none.  Windows of up to DOMALIGN_MAX_WIN residues; the tables as
+        dom_search takes them."""
+        n, chrom, start, end, frame, i0, i1 = self._items(chrom, start, end, frame, i0, i1)
+        prof = np.ascontiguousarray(prof, np.int32)
+        moff, entry = np.ascontiguousarray(moff, np.int32), np.ascontiguousarray(entry, np.int32)
+        emis, trans = np.ascontiguousarray(emis, np.int32), np.ascontiguousarray(trans, np.int32)
+        P = int(moff.size) - 1
+        if prof.size != n:
+            raise ValueError("prof must have one entry per item")
+        if P >= 1 and (entry.size != P or emis.size != int(moff[-1]) * 22 or trans.size != int(moff[-1]) * 7):
+            raise ValueError("the tables must have entry [P], emis [sum M, 22] and trans [sum M, 7] for moff [P + 1]")
+        ok = P >= 1 and n > 0 and int(prof.min()) >= 0 and int(prof.max()) < P
+        width = (moff[1:] - moff[:-1]).astype(np.int64)[prof] if ok else np.zeros(n, np.int64)      # (a bad prof: the library says so)
+        coff = np.concatenate((np.zeros(1, np.int64), np.cumsum(width))).astype(np.int64)
+        hit, col = np.empty((n, 5), np.int32), np.empty(max(int(coff[-1]), 1), np.int32)
+        self._ck(self.L.sp_dom_align(self.h, n, _p(chrom), _p(start), _p(end), _p(frame), _p(i0), _p(i1), _p(prof), P, _p(moff), _p(emis), _p(trans),
+                                     _p(entry), _p(hit), _p(coff), _p(col)))
+        return hit, col[:int(coff[-1])], coff
+
+    def dom_align_set_batch(self, items=0):
+        """the most items a batch of dom_align takes (0: the default, by the workspace cap); results do not depend on it"""
+        self._ck(self.L.sp_dom_align_set_batch(self.h, int(items)))
+
+    def dom_peptide(self, chrom, start, end, frame, i0, i1):
+        """The residue codes of the windows (sp_dom_peptide): (pep uint8, flat; poff int64 [n + 1]); the letter of code c
+        is PEPTIDE_LETTERS[c]."""
+        n, chrom, start, end, frame, i0, i1 = self._items(chrom, start, end, frame, i0, i1)
+        poff = np.concatenate((np.zeros(1, np.int64), np.cumsum(i1.astype(np.int64) - i0 + 1))).astype(np.int64)
+        pep = np.empty(max(int(poff[-1]), 1) if n and int(poff.min()) >= 0 else 1, np.uint8)
+        self._ck(self.L.sp_dom_peptide(self.h, n, _p(chrom), _p(start), _p(end), _p(frame), _p(i0), _p(i1), _p(poff), _p(pep)))
+        return pep[:max(int(poff[-1]), 0)], poff
+
+    def aln_pairs(self, rows):
+        """(same, both), int32 [N, N] each, of all pairs of the N aligned rows (uint8 [N, C]; 0..19 residues, anything
+        else no residue) (sp_aln_pairs): the columns where both rows hold a residue, and those where the two are equal."""
+        rows = np.ascontiguousarray(rows, np.uint8)
+        if rows.ndim != 2:
+            raise ValueError("rows must be N x C")
+        N, Cn = rows.shape
+        same, both = np.empty((N, N), np.int32), np.empty((N, N), np.int32)
+        self._ck(self.L.sp_aln_pairs(self.h, int(N), int(Cn), _p(rows), _p(same), _p(both)))
+        return same, both
 
     def nj_tree(self, dist):
         """Neighbour joining on a symmetric int64 [N, N] matrix with zero diagonal and entries in [0, 2^31)

@@ -78,3 +78,27 @@ SP_SWAR_HD uint32_t sp_swar_any_ge255(uint32_t a, uint32_t b, uint32_t c, uint32
     const uint32_t mx = sp_swar_max16(sp_swar_max16(a, b), sp_swar_max16(c, d));
     return (sp_swar_min16(mx, 0x00ff00ffu) + 0x00010001u) & 0x01000100u;
 }
+
+// ---- eight bytes per 64-bit word (the pair comparison of aligned rows, sp_domalign.hip)
+// bit 7 of a byte of the result is set iff that byte of w is below 20 (a residue code).  (x & 0x7f) + 108 reaches bit 7
+// iff the low seven bits are >= 20, and a byte with bit 7 set is >= 128; no carry leaves a byte: 127 + 108 < 256.
+SP_SWAR_HD uint64_t sp_swar_lt20_bytes(uint64_t w) {
+    const uint64_t t = (w & 0x7f7f7f7f7f7f7f7fULL) + 0x6c6c6c6c6c6c6c6cULL;
+    return ~(t | w) & 0x8080808080808080ULL;
+}
+// bit 7 of a byte of the result is set iff that byte of a equals that byte of b: (x & 0x7f) + 127 reaches bit 7 iff the
+// low seven bits of x = a ^ b are not all zero
+SP_SWAR_HD uint64_t sp_swar_eq_bytes(uint64_t a, uint64_t b) {
+    const uint64_t x = a ^ b, t = (x & 0x7f7f7f7f7f7f7f7fULL) + 0x7f7f7f7f7f7f7f7fULL;
+    return ~(t | x) & 0x8080808080808080ULL;
+}
+// number of flagged bytes
+SP_SWAR_HD uint32_t sp_swar_byte_count(uint64_t flags) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_popcountll(flags);
+#else
+    uint32_t n = 0;
+    for (int q = 7; q < 64; q += 8) n += (uint32_t)(flags >> q & 1ULL);
+    return n;
+#endif
+}

@@ -191,7 +191,7 @@ def parse_name(name):
 # ------------------------------------------------------------------------------------------------ hits
 class Domain:
     """one line of `.ltr.dom.gff3`"""
-    __slots__ = ("element", "seqid", "start", "end", "score", "strand", "frame", "profile", "gene", "clade", "full", "coverage", "raw")
+    __slots__ = ("element", "seqid", "start", "end", "score", "strand", "frame", "profile", "gene", "clade", "full", "coverage", "raw", "pidx", "hit")
 
     def attributes(self):
         return "ID={}|{};Name={}-{};gene={};clade={};coverage={};score={}".format(
@@ -253,6 +253,7 @@ def best_domains(ids, lengths, hits, profiles, min_cov=MIN_COV, min_score=MIN_SC
                 continue
             d = Domain()
             d.element, d.profile, d.raw = eid, profiles.names[p], s
+            d.pidx, d.hit = p, (frame, i0, i1)      # the profile's index and (frame 0..5, i_start, i_end): what the domain trees align
             d.seqid, d.start, d.end, d.strand, d.frame = coordinates(eid, frame, i0, i1, int(lengths[e]))
             d.score = round(s / float(SCALE * M), 2)
             d.coverage = round(1e2 * (k1 - k0 + 1) / M, 1)

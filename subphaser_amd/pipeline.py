@@ -27,8 +27,11 @@ seeds, gapless extension; ltr.detect: the loop over the chromosomes and the chai
 -ltr_tree the subgenome-specific elements get ONE tree of this build's own: MinHash sketches and neighbour joining on the
 device (ltrtree.py, csrc/sp_ltrtree.hip), `.ltr.tree.nwk` / `.map` and a figure.  With -ltr_hmm the records are classified
 from the protein domains of their inner sequences first (domains.py, csrc/sp_domains.hip: this build's own Viterbi search of the
-user's profile HMMs, TEsorter's rules behind it): `.ltr.dom.gff3`, `.ltr.cls.tsv`, records that are no LTR-RTs dropped.  ltr_finder / ltrharvest themselves,
-TEsorter, the reference's protein-domain trees and the circos figure itself stay with the reference.
+user's profile HMMs, TEsorter's rules behind it): `.ltr.dom.gff3`, `.ltr.cls.tsv`, records that are no LTR-RTs dropped.  With
+-ltr_domtree (and -ltr_hmm) the subgenome-specific elements that have all of -ltr_domains get one tree per Copia / Gypsy from
+their domains (domtree.py, csrc/sp_domalign.hip: this build's own profile alignment, occupancy trimming, Kimura distances and
+neighbour joining): `.ltr.cls.pep` and `.ltr.LTR_<Superfamily>.aln` / `.map` / `.aln.trimmed` / `.aln.rooted.tre` and a figure.
+ltr_finder / ltrharvest themselves, TEsorter, mafft / trimal / iqtree and the circos figure itself stay with the reference.
 """
 import argparse
 import io
@@ -45,6 +48,7 @@ from . import REFERENCE_VERSION, __version__
 from . import blocks as blocks_mod
 from . import domains as domains_mod
 from . import ltr as ltr_mod
+from . import domtree as domtree_mod
 from . import ltrtree as ltrtree_mod
 from . import circos, seqs, stats
 from .cluster import BOOTSTRAP_ENGINES, TEST_METHODS, Cluster
@@ -137,7 +141,8 @@ CLI = [
             "TEsorter itself and the LTR trees): the stage runs when -ltr_scn or -ltr_denovo is given, unless -just_core or "
             "-disable_ltr; without -ltr_hmm every record is used, as under -all_ltr; -mu, -exclude_exchanges and -non_specific are honoured; "
             "-ltr_tree adds this build's own tree of the subgenome-specific elements (-subsample and -disable_ltrtree are used); "
-            "-ltr_hmm classifies the records from protein domains and drops those that are no LTR-RTs (-all_ltr keeps them)", [
+            "-ltr_hmm classifies the records from protein domains and drops those that are no LTR-RTs (-all_ltr keeps them); "
+            "-ltr_domtree adds this build's own tree per Copia / Gypsy from the domains (-ltr_domains, -subsample, -disable_ltrtree are used)", [
         (("-ltr_scn",), dict(type=str, metavar="FILE", default=None,
                              help="LTR-RTs in the 12-column format of the reference's tmp/LTR.scn (ltrharvest's columns plus the "
                                   "sequence id)")),
@@ -188,6 +193,20 @@ CLI = [
                                 help="k-mer size of the tree's sketches, odd, 9..31; provisional: judged on synthetic families only")),
         (("-ltr_tree_sketch",), dict(type=int, metavar="INT", default=ltrtree_mod.TREE_SKETCH,
                                      help="hashes per sketch, 16..4096; provisional: judged on synthetic families only")),
+        (("-ltr_domtree",), dict(help="build one tree per Copia / Gypsy from the protein domains of the subgenome-specific "
+                                      "LTR-RTs (needs -ltr_hmm): `.ltr.cls.pep`, and per superfamily `.ltr.LTR_<Superfamily>.aln`, "
+                                      "`.map`, `.aln.trimmed`, `.aln.rooted.tre` and `.tree.<figfmt>`.  The elements with all of "
+                                      "-ltr_domains (default INT RT RH) are aligned on the GPU to one profile per domain by this "
+                                      "build's own Viterbi path, columns below -ltr_tree_occupancy are dropped, Kimura distances "
+                                      "and neighbour joining give the tree.  Not mafft, trimal or iqtree, and never compared with "
+                                      "them; inserted residues appear in no column.  At most -subsample elements (4096 at most) "
+                                      "per tree; -disable_ltrtree wins; independent of -ltr_tree", **_FLAG)),
+        (("-ltr_tree_occupancy",), dict(type=int, metavar="INT", default=domtree_mod.OCCUPANCY,
+                                        help="percent of the rows that must hold a residue for a column of the domain alignment to "
+                                             "stay; provisional")),
+        (("-ltr_tree_overlap",), dict(type=int, metavar="INT", default=domtree_mod.OVERLAP,
+                                      help="columns two rows of the domain alignment must share; below it their distance is the "
+                                           "largest one; provisional")),
     ]),
     ("Other options", None, [
         (("-p", "-ncpu"), dict(dest="ncpu", type=int, metavar="INT", default=NCPU)),
@@ -229,6 +248,8 @@ def makeArgparse(argv=None):
     args = parser.parse_args(argv)
     if args.ltr_denovo and args.ltr_scn:
         parser.error("-ltr_denovo detects the LTR-RTs, -ltr_scn reads them from a file: give one of the two")
+    if args.ltr_domtree and not args.ltr_hmm:
+        parser.error("-ltr_domtree builds its trees from the domains of the classification: give -ltr_hmm FILE as well")
     if args.prefix is not None:          # the prefix goes in front of directory names AND file names (__main__.py:242-245)
         args.prefix = args.prefix.replace("/", "_")
         args.outdir, args.tmpdir = args.prefix + args.outdir, args.prefix + args.tmpdir
@@ -292,6 +313,8 @@ class Pipeline:
     # caller gave.  So an object put together by hand -- Pipeline.__new__ and some attributes -- reads the parser's defaults
     # for the rest, too.
     _ltr_tree_built = False      # stage_ltr wrote a tree (it starts by putting this back): _run words its closing note by it
+    _ltr_domtrees_built = ()     # the superfamilies whose domain tree stage_ltr wrote (-ltr_domtree), likewise
+    _ltr_dominfo = None          # what _ltr_classify keeps for the domain trees: domains, class rows, inner intervals
 
     def _configure(self, opts):
         """the state of a run and the caller's options (the others are the class's defaults); -colors as a list or None"""
@@ -742,6 +765,17 @@ class Pipeline:
         if want_tree and not all(hasattr(ctx, m) for m in ("ltr_sketch", "ltr_sketch_pairs", "nj_tree")):      # before anything is written
             raise RuntimeError("-ltr_tree needs a context with ltr_sketch, ltr_sketch_pairs and nj_tree (libsubphaser_hip.so); there "
                                "is no CPU engine for the tree")
+        self._ltr_domtrees_built, self._ltr_dominfo = (), None
+        want_domtree = self.ltr_domtree
+        if want_domtree and self.disable_ltrtree:
+            logger.info("-disable_ltrtree: the domain trees of -ltr_domtree are not built")
+            want_domtree = False
+        if want_domtree and not self.ltr_hmm:
+            raise ValueError("-ltr_domtree builds its trees from the domains of the classification: give -ltr_hmm FILE as well")
+        if want_domtree and not all(hasattr(ctx, m) for m in domtree_mod.REQUIRED):      # before anything is written
+            raise RuntimeError("-ltr_domtree needs a context with dom_align, dom_peptide, aln_pairs and nj_tree (libsubphaser_hip.so); "
+                               "there is no CPU engine for the domain trees")
+        self._want_domtree = bool(want_domtree)
         self._ltr_profiles, self._ltr_clades = None, {}
         if self.ltr_hmm:
             if not hasattr(ctx, "dom_search"):      # before anything is written
@@ -765,8 +799,11 @@ class Pipeline:
         if not d_enriched:
             logger.warning("Because of none subgenome-specific LTR-RTs, plots of LTR-RTs are skipped.")
             return
-        if self._ltr_insert(lay, ltrs, ages, d_enriched, d_exchange, list(cl.sg_names)) and want_tree:
+        dated = self._ltr_insert(lay, ltrs, ages, d_enriched, d_exchange, list(cl.sg_names))
+        if dated and want_tree:
             self._ltr_tree(lay, ctx, ltrs, chrom, st, en, d_enriched, d_exchange, list(cl.sg_names))
+        if dated and want_domtree:
+            self._ltr_domtree(lay, ctx, ltrs, d_enriched, d_exchange, list(cl.sg_names))
 
     def _ltr_detected(self, lay, labels, ctx, band):
         """-ltr_denovo: (records, path) of the LTR-RTs ltr.detect finds, written to `.ltr.scn`; there is no CPU detector"""
@@ -821,6 +858,9 @@ class Pipeline:
         logger.info("{} inner sequences x {} profiles searched in {:.2f} s: {} domains (coverage >= {}, score >= {} bits per node) in {} "
                     "elements -> `{}`, `{}`".format(len(pick), len(profiles), time.perf_counter() - t0, len(doms), self.ltr_dom_cov,
                                                     self.ltr_dom_score, len(rows), os.path.basename(gff), os.path.basename(cls)))
+        if self._want_domtree:
+            self._ltr_dominfo = dict(doms=doms, rows=rows, where={known[q].id: (index[known[q].seq_id],) + tuple(ival[q]) for q in pick})
+            self._ltr_pep(lay, ctx)
         d_class = {r[0]: r for r in rows}
         kept, completed, n_ltr, n_intact = [], set(), 0, 0
         for r in known:
@@ -982,6 +1022,111 @@ class Pipeline:
         self._ltr_tree_built = True
         self._plot_later(lay, "LTR tree", [fig], lambda: ltrtree_mod.plot(fig, records, sgs, self._sg_colors(sg_names)))
 
+    _want_domtree = False
+
+    def _ltr_pep(self, lay, ctx):
+        """-ltr_domtree: `.ltr.cls.pep`, the peptide of every line of `.ltr.dom.gff3` in the shape of TEsorter's `.cls.pep`"""
+        info = self._ltr_dominfo
+        doms, where = info["doms"], info["where"]
+        place = [where[d.element] for d in doms]
+        peps = domtree_mod.peptides_of(ctx, np.array([p[0] for p in place], np.int32), np.array([p[1] for p in place], np.int64),
+                                       np.array([p[2] for p in place], np.int64), np.array([d.hit[0] for d in doms], np.int32),
+                                       np.array([d.hit[1] for d in doms], np.int32), np.array([d.hit[2] for d in doms], np.int32))
+        pep = lay.out("ltr.cls.pep")
+        with open(pep, "w") as fout:
+            domtree_mod.write_pep(fout, doms, info["rows"], peps)
+        mk_ckp(lay.ckp(pep))
+        logger.info("{} domain peptides -> `{}`".format(len(doms), os.path.basename(pep)))
+
+    def _ltr_domtree(self, lay, ctx, ltrs, d_enriched, d_exchange, sg_names):
+        """-ltr_domtree: per Copia / Gypsy `.ltr.LTR_<Superfamily>.aln`, `.map`, `.aln.trimmed`, `.aln.rooted.tre` and
+        `.tree.<figfmt>` over the elements `.ltr.insert.data` lists as subgenome-specific (without the exchanged ones under
+        -exclude_exchanges) that have every domain of -ltr_domains (LTR.LTRtree, LTR.py:144-233).  The trees are this build's
+        own objects (domtree.py): profile alignment, occupancy trimming, Kimura distances and neighbour joining on the device."""
+        if self.trimal_options:
+            logger.warning("-trimal_options {}: trimal is not run; the columns of the domain alignments are kept by "
+                           "-ltr_tree_occupancy {}".format(self.trimal_options, self.ltr_tree_occupancy))
+        wanted = list(self.ltr_domains) if self.ltr_domains else list(domtree_mod.DOMAINS)
+        limit, seed = int(self.subsample), self.bootstrap_seed
+        occupancy, overlap = int(self.ltr_tree_occupancy), int(self.ltr_tree_overlap)
+        if limit < 0:
+            raise ValueError("-subsample {} is below 0".format(limit))
+        if not 0 <= occupancy <= 100 or overlap < 0:
+            raise ValueError("-ltr_tree_occupancy {} is outside 0..100 or -ltr_tree_overlap {} is below 0".format(occupancy, overlap))
+        info, gid = self._ltr_dominfo, domains_mod.format_gff_id
+        elem_domains = {}
+        for d in info["doms"]:
+            elem_domains.setdefault(d.element, {}).setdefault(d.gene, d)
+        by_id = {x[0]: x for x in info["rows"]}
+        classes = {r.id: (by_id[gid(r.id)][1], by_id[gid(r.id)][2]) for r in ltrs if gid(r.id) in by_id}
+        candidates = [r.id for r in ltrs if r.id in d_enriched and not (self.exclude_exchanges and d_exchange.get(r.id) == "yes")]
+        built = []
+        for order, superfamily in domtree_mod.CATEGORIES:
+            key = "{}_{}".format(order, superfamily)
+            logger.info("Extracting and aligning protein domain sequences of {}/{}".format(order, superfamily))
+            selected, counts = domtree_mod.select(candidates, elem_domains, classes, order, superfamily, wanted)
+            for dom in wanted:
+                logger.info("{} sequences contain {} domains".format(counts[dom], dom))
+            logger.info("{} sequences contain all {} domains".format(len(selected), wanted))
+            cap = min(limit, domtree_mod.MAX_N) if limit else domtree_mod.MAX_N
+            if len(selected) > cap:
+                logger.info("Subsample {} / {} ({:.2%})".format(cap, len(selected), cap / len(selected)))
+                selected = [selected[q] for q in ltrtree_mod.choose(len(selected), cap, 0 if seed is None else seed)]
+            t0 = time.perf_counter()
+            kept_ids, blocks, common, left = domtree_mod.align_category(ctx, selected, elem_domains, info["where"], wanted, self._ltr_profiles) \
+                if selected else ([], [[] for _ in wanted], {}, [])
+            if left:
+                logger.info("{}: {} elements with a window above {} residues are left out".format(key, len(left), domtree_mod.MAX_WIN))
+            for dom in wanted:
+                if dom in common:
+                    logger.info("{}: {} is aligned to profile `{}`".format(key, dom, self._ltr_profiles.names[common[dom]]))
+            t_align = time.perf_counter() - t0
+            labels = [domtree_mod.format_id_for_iqtree(gid(e).split("#")[0]) for e in kept_ids]
+            description, records, dropped = domtree_mod.cat_rows(labels, blocks, unique=True)
+            aln, amap = lay.out("ltr.{}.aln".format(key)), lay.out("ltr.{}.map".format(key))
+            with open(aln, "w") as fout:
+                domtree_mod.write_aln(fout, records, description)
+            mk_ckp(lay.ckp(aln), len(kept_ids))
+            if kept_ids:
+                logger.info("{} ({:.1%}) unique alignments retained".format(len(records), 1 - dropped / len(kept_ids)))
+            else:
+                logger.warning("0 sequences")
+            with open(amap, "w") as fout:
+                # every selected element, as the reference's: those left out for their window included
+                ltrtree_mod.write_map(fout, [domtree_mod.format_id_for_iqtree(gid(e).split("#")[0]) for e in selected],
+                                      [d_enriched[e] for e in selected], [self._ltr_clades.get(e, "unknown") for e in selected])
+            mk_ckp(lay.ckp(amap))
+            if len(records) < ltrtree_mod.MIN_SEQS:
+                logger.info("{}: {} aligned rows, fewer than {}: no tree".format(key, len(records), ltrtree_mod.MIN_SEQS))
+                continue
+            names = [n for n, _ in records]
+            trimmed = domtree_mod.trim([row for _, row in records], occupancy)
+            trimfile = aln + ".trimmed"
+            with open(trimfile, "w") as fout:
+                domtree_mod.write_aln(fout, list(zip(names, trimmed)), description)
+            mk_ckp(lay.ckp(trimfile))
+            width = len(trimmed[0])
+            if not 1 <= width <= domtree_mod.MAX_C:
+                logger.info("{}: {} columns stay at -ltr_tree_occupancy {} (1 to {} are taken): no tree".format(key, width, occupancy, domtree_mod.MAX_C))
+                continue
+            t1 = time.perf_counter()
+            same, both = ctx.aln_pairs(domtree_mod.encode(trimmed))
+            D = domtree_mod.distance_matrix(same, both, overlap)
+            t2 = time.perf_counter()
+            records_nj = np.asarray(ctx.nj_tree(D), np.int64)
+            logger.info("{} tree of {} rows x {} columns ({} before trimming): alignment {:.2f} s, pairs {:.2f} s, neighbour joining {:.2f} s".format(
+                key, len(names), width, len(records[0][1]), t_align, t2 - t1, time.perf_counter() - t2))
+            tre, fig = aln + ".rooted.tre", lay.out("ltr.{}.tree.{}".format(key, self.figfmt))
+            with open(tre, "w") as fout:
+                fout.write(ltrtree_mod.tree_text(records_nj, names) + "\n")
+            mk_ckp(lay.ckp(tre))
+            sg_of = dict(zip(labels, [d_enriched[e] for e in kept_ids]))
+            sgs = [sg_of[n] for n in names]
+            built.append(superfamily)
+            self._plot_later(lay, "LTR {} domain tree".format(superfamily), [fig],
+                             lambda fig=fig, rec=records_nj, sgs=sgs: ltrtree_mod.plot(fig, rec, sgs, self._sg_colors(sg_names)))
+        self._ltr_domtrees_built = tuple(built)
+
     def run(self):
         self._reset()
         try:
@@ -1017,15 +1162,18 @@ class Pipeline:
                 self.stage_ltr(lay, labels, cl, kmer_labels)
                 # the closing note: what of modules 3-4 this run did not do itself
                 missing = (([] if denovo else ["LTR detection"]) + ([] if self.ltr_hmm else ["TEsorter classification"])
-                           + ([] if self._ltr_tree_built else ["the LTR trees"]))
-                logger.info("Of modules 3-4, {}the circos figure {} not part of this build{}{}{}; run the reference on the outputs above "
+                           + ([] if self._ltr_tree_built or self._ltr_domtrees_built else ["the LTR trees"]))
+                logger.info("Of modules 3-4, {}the circos figure {} not part of this build{}{}{}{}; run the reference on the outputs above "
                             "for {}".format(
                                 ", ".join(missing) + " and " if missing else "", "are" if missing else "is",
                                 "; the classification is this build's own Viterbi domain search (-ltr_hmm), not TEsorter's hmmscan"
                                 if self.ltr_hmm else "",
                                 " (the LTR-RTs are this build's own detection, not ltr_finder's or ltrharvest's)" if denovo else "",
                                 "; the tree of -ltr_tree is this build's own (sketches and neighbour joining), not the reference's domain "
-                                "trees" if self._ltr_tree_built else "", "them" if missing else "it"))
+                                "trees" if self._ltr_tree_built else "",
+                                "; the domain trees of -ltr_domtree ({}) are built and are this build's own (profile alignment, Kimura "
+                                "distances, neighbour joining), not mafft / trimal / iqtree trees".format(", ".join(self._ltr_domtrees_built))
+                                if self._ltr_domtrees_built else "", "them" if missing else "it"))
             elif not (self.disable_ltr and self.disable_circos):
                 logger.info("Modules 3-4 (LTR, circos) are not part of this build; run the reference on the "
                             "outputs above, or pass -disable_ltr -disable_circos to silence this note")
