@@ -503,13 +503,30 @@ int sp_nj_set_guard(sp_ctx *ctx, int64_t limit);
  *                   per (element, profile) = score, frame (0..2 forward, 3..5 reverse complement), i_start, i_end (residues
  *                   of the frame, 0-based, inclusive), k_start, k_end (nodes, 1-based, inclusive); no residue in any
  *                   frame: INT32_MIN and zeros.  One wave per (element, frame, profile), longest first.  n = 0 is fine.
+ *   sp_dom_ssv      the ungapped prefilter score (csrc/sp_domains.h: the search's recurrence restricted to the match
+ *                   states; never above the score of the frame's hit) of every (element, profile, frame), arguments as
+ *                   sp_dom_search: out n x P x 6 int32, one score per FRAME, INT32_MIN where the frame has no residue.
+ *   sp_dom_search_pre  sp_dom_search behind the prefilter: only the (frame, profile) items with ssv >= threshold are
+ *                   searched, a frame that does not pass has no hit, and an (element, profile) without a passing frame
+ *                   is INT32_MIN and zeros.  A HEURISTIC: a domain whose best ungapped segment scores below the threshold
+ *                   is lost.  threshold = INT32_MIN is sp_dom_search, byte for byte.  stats[0] = the items with
+ *                   residues, stats[1] = those that passed.  The scores go to the host, which lists the survivors.
+ *   sp_dom_ssv_set_tile  nodes a tile of the prefilter kernel holds (1..128) and diagonals a workgroup of it walks
+ *                   (1..1024); 0 = the default, 128 and 1024; tests use small values -- no result depends on them
  * SP_EINVAL: a NULL pointer; no genome; a chromosome out of range; an interval off its chromosome or with end < start;
  * P < 1; offsets that do not ascend from 0 (an M < 1); a transition or entry outside [-2^20, 0] or an emission outside
- * [-2^20, 2^15] -- all checked on the host before any launch.  SP_EUNSUP: M > 2048, an interval above 65536 bases,
- * P > 4096, n x P > 2^24 -- decided before any allocation.  SP_ENOMEM: the workspace does not fit (the message has its
- * size).                                                                                                                  */
+ * [-2^20, 2^15]; a tile or span outside its range -- all checked on the host before any launch.  SP_EUNSUP: M > 2048,
+ * an interval above 65536 bases, P > 4096, n x P > 2^24, more than 2^31 - 1 workgroups of the prefilter -- decided
+ * before any allocation.  SP_ENOMEM: the workspace does not fit (the message has its size).  The three entries share
+ * their checks: the same refusals, the same codes.                                                                         */
 int sp_dom_search(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int P,
                   const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry, int32_t *out);
+int sp_dom_ssv(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int P,
+               const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry, int32_t *out);
+int sp_dom_search_pre(sp_ctx *ctx, int64_t n, const int32_t *chrom, const int64_t *start, const int64_t *end, int P,
+                      const int32_t *moff, const int32_t *emis, const int32_t *trans, const int32_t *entry,
+                      int32_t threshold, int32_t *out, int64_t *stats);
+int sp_dom_ssv_set_tile(sp_ctx *ctx, int nodes, int span);
 
 /* ---- LTR-RT domain trees: profile alignment with traceback, peptides, pairwise comparison of aligned rows ------
  * The alignment is defined by integer arithmetic (csrc/sp_domalign.h holds the definition: the item, the back-pointer

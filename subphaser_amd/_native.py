@@ -46,7 +46,7 @@ SYMBOLS = [
     "sp_blocks_index", "sp_blocks_pair", "sp_blocks_anchors", "sp_blocks_release", "sp_blocks_set_cells",
     "sp_ltr_align", "sp_ltr_seeds", "sp_ltr_hsps", "sp_ltr_detect_set_chunk", "sp_ltr_detect_set_capacity",
     "sp_ltr_sketch", "sp_ltr_sketch_set_chunk", "sp_ltr_sketch_pairs", "sp_nj_tree", "sp_nj_set_mode", "sp_nj_set_guard",
-    "sp_dom_search",
+    "sp_dom_search", "sp_dom_ssv", "sp_dom_search_pre", "sp_dom_ssv_set_tile",
     "sp_dom_align", "sp_dom_align_set_batch", "sp_dom_peptide", "sp_aln_pairs",
     "sp_sparse_sizes", "sp_sparse_sample", "sp_sparse_split", "sp_sparse_export", "sp_sparse_view",
     "sp_prof_enable", "sp_prof_reset", "sp_prof_report",
@@ -156,6 +156,9 @@ def load():
     L.sp_ltr_sketch.argtypes = [vp, i64, vp, vp, vp, ci, ci, vp, vp]
     L.sp_ltr_sketch_set_chunk.argtypes = [vp, ci]
     L.sp_dom_search.argtypes = [vp, i64, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.sp_dom_ssv.argtypes = [vp, i64, vp, vp, vp, ci, vp, vp, vp, vp, vp]
+    L.sp_dom_search_pre.argtypes = [vp, i64, vp, vp, vp, ci, vp, vp, vp, vp, C.c_int32, vp, vp]
+    L.sp_dom_ssv_set_tile.argtypes = [vp, ci, ci]
     L.sp_dom_align.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, ci, vp, vp, vp, vp, vp, vp, vp]
     L.sp_dom_align_set_batch.argtypes = [vp, i64]
     L.sp_dom_peptide.argtypes = [vp, i64, vp, vp, vp, vp, vp, vp, vp, vp]
@@ -1058,14 +1061,8 @@ class Context:
         return shared, denom
 
     # -------------------------------------------------------------- LTR domains
-    def dom_search(self, chrom, start, end, moff, emis, trans, entry):
-        """Local Viterbi search of P profile HMMs in the six-frame translation of the intervals [start, end) (0-based,
-        half-open; an empty one has no hit) on the resident genome (sp_dom_search; definition in csrc/sp_domains.h):
-        int32 [n, P, 6] = score (1/256 bit), frame, i_start, i_end, k_start, k_end; INT32_MIN and zeros where no frame has
-        a residue.  moff int32 [P + 1], emis int32 [sum M, 22], trans int32 [sum M, 7], entry int32 [P] (domains.read_hmm
-        makes them).  The elements go in calls of at most DOMAINS_CALL_ENTRIES (element, profile) entries -- far below the
-        library's limit DOMAINS_MAX_ENTRIES, so that the host lists of a call stay small; a profile set above that alone
-        goes an element at a time."""
+    @staticmethod
+    def _dom_args(chrom, start, end, moff, emis, trans, entry):
         chrom = np.ascontiguousarray(chrom, np.int32)
         start, end = np.ascontiguousarray(start, np.int64), np.ascontiguousarray(end, np.int64)
         moff, entry = np.ascontiguousarray(moff, np.int32), np.ascontiguousarray(entry, np.int32)
@@ -1075,13 +1072,55 @@ class Context:
             raise ValueError("chrom, start and end must have one entry per element")
         if P >= 1 and (entry.size != P or emis.size != int(moff[-1]) * 22 or trans.size != int(moff[-1]) * 7):
             raise ValueError("the tables must have entry [P], emis [sum M, 22] and trans [sum M, 7] for moff [P + 1]")
+        return n, P, chrom, start, end, moff, emis, trans, entry
+
+    def dom_search(self, chrom, start, end, moff, emis, trans, entry, prefilter=None, stats=None):
+        """Local Viterbi search of P profile HMMs in the six-frame translation of the intervals [start, end) (0-based,
+        half-open; an empty one has no hit) on the resident genome (sp_dom_search; definition in csrc/sp_domains.h):
+        int32 [n, P, 6] = score (1/256 bit), frame, i_start, i_end, k_start, k_end; INT32_MIN and zeros where no frame has
+        a residue.  moff int32 [P + 1], emis int32 [sum M, 22], trans int32 [sum M, 7], entry int32 [P] (domains.read_hmm
+        makes them).  The elements go in calls of at most DOMAINS_CALL_ENTRIES (element, profile) entries -- far below the
+        library's limit DOMAINS_MAX_ENTRIES, so that the host lists of a call stay small; a profile set above that alone
+        goes an element at a time.
+        prefilter: None is sp_dom_search; an integer T (1/256 bit) is sp_dom_search_pre -- only the (frame, profile) items
+        whose ungapped score (dom_ssv) is at least T are searched, a heuristic: a domain whose best ungapped segment
+        scores below T is lost.  stats, a dict, then receives `items` (the items with residues) and `passed`, summed over
+        the calls."""
+        n, P, chrom, start, end, moff, emis, trans, entry = self._dom_args(chrom, start, end, moff, emis, trans, entry)
+        out = np.empty((n, max(P, 0), 6), np.int32)
+        step = max(1, DOMAINS_CALL_ENTRIES // max(P, 1))
+        counts = np.zeros(2, np.int64)
+        for a in range(0, max(n, 1), step):
+            b = min(n, a + step)
+            if prefilter is None:
+                self._ck(self.L.sp_dom_search(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans),
+                                              _p(entry), _p(out[a:b])))
+                continue
+            part = np.zeros(2, np.int64)
+            self._ck(self.L.sp_dom_search_pre(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans),
+                                              _p(entry), int(prefilter), _p(out[a:b]), _p(part)))
+            counts += part
+        if stats is not None and prefilter is not None:
+            stats["items"] = stats.get("items", 0) + int(counts[0])
+            stats["passed"] = stats.get("passed", 0) + int(counts[1])
+        return out
+
+    def dom_ssv(self, chrom, start, end, moff, emis, trans, entry):
+        """The ungapped prefilter score (sp_dom_ssv; definition in csrc/sp_domains.h) of every (element, profile, frame),
+        arguments as dom_search: int32 [n, P, 6], one score per frame (1/256 bit), INT32_MIN where the frame has no
+        residue.  Never above the score of the frame's hit."""
+        n, P, chrom, start, end, moff, emis, trans, entry = self._dom_args(chrom, start, end, moff, emis, trans, entry)
         out = np.empty((n, max(P, 0), 6), np.int32)
         step = max(1, DOMAINS_CALL_ENTRIES // max(P, 1))
         for a in range(0, max(n, 1), step):
             b = min(n, a + step)
-            self._ck(self.L.sp_dom_search(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans),
-                                          _p(entry), _p(out[a:b])))
+            self._ck(self.L.sp_dom_ssv(self.h, b - a, _p(chrom[a:b]), _p(start[a:b]), _p(end[a:b]), P, _p(moff), _p(emis), _p(trans), _p(entry),
+                                       _p(out[a:b])))
         return out
+
+    def dom_ssv_set_tile(self, nodes=0, span=0):
+        """nodes of a tile and diagonals of a workgroup of the prefilter kernel (0: the defaults); results do not depend on them"""
+        self._ck(self.L.sp_dom_ssv_set_tile(self.h, int(nodes), int(span)))
 
     # -------------------------------------------------------------- LTR domain trees
     @staticmethod

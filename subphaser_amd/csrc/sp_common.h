@@ -218,6 +218,8 @@ struct sp_ctx {
     int lt_mode = 0;        // see sp_ltr_sketch_set_chunk / sp_nj_set_mode
     int64_t lt_guard = 0;   // the guard of the joins (0: SP_LT_DMAX), see sp_nj_set_guard
     int64_t da_batch = 0;   // most items a batch of sp_dom_align takes (0: by the workspace cap), see sp_dom_align_set_batch
+    int ds_tile = 0;        // nodes a tile of dm_ssv holds and diagonals a workgroup of it walks (0: the defaults), see
+    int ds_span = 0;        // sp_dom_ssv_set_tile
     sp_buf b_wtab, b_enr;   // window table (device) and the enrichment outputs
     sp_blocks_state *blocks = nullptr;   // per-chromosome single-copy k-mer indexes of the block stage (sp_blocks.hip)
     sp_ltrdetect_state *ltrdetect = nullptr;   // chunk size, seed capacity and the last HSP list of the LTR detection (sp_ltrdetect.hip)

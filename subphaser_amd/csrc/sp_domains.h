@@ -40,6 +40,20 @@
 //   of the pairs.  INT64_MIN is no such word (|w| < 2^63 - 2^26) and stands for "does not exist" (SP_DM_NONE).
 //   The hit's score fits int32: the best cell is at least a one-cell path, entry + e >= -2^21, and at most 21845 emissions of
 //   at most 2^15 each with transitions and entry <= 0: below 2^15 * 2^15 = 2^30.
+//
+// The ungapped prefilter (SSV).  The score of one frame against one profile is the recurrence above restricted to the
+//   match states -- the best ungapped segment, a score only: no start, no end, no tie rule:
+//     S[i][k] = e[k][x_i] + max( entry, S[i-1][k-1] + tMM[k-1] )        (the second term only when i >= 1 and k >= 2)
+//     ssv     = max over all cells S[i][k];  a frame without residues has none (INT32_MIN)
+//   Tables, columns and entry are those of M[i][k]; tMM[k-1] is trans[7 (k - 2) + SP_DM_MM].  A cell depends on its
+//   diagonal i - k alone, and the maximum is one of integers: no result depends on the order the cells are visited in.
+//   Range.  S >= entry + e >= -2^21.  S is at most 21845 emissions of at most 2^15 each (transitions and entry <= 0), so
+//   S < 21845 * 2^15 < 2^30.  A predecessor that does not exist is SP_DM_SSV_NONE = -2^30: NONE + tMM >= -2^30 - 2^20 does
+//   not wrap and lies below every entry (>= -2^20), so the max takes the entry.  int32 throughout, no saturation.
+//   Bound.  S[i][k] <= score(M[i][k]) by induction over the cells: both take the entry, M[i][k] takes the maximum over a
+//   superset of S's terms, and S[i-1][k-1] <= score(M[i-1][k-1]) is the hypothesis.  Hence ssv <= the score of the frame's
+//   Viterbi hit.  A search that keeps only the frames with ssv >= T is a HEURISTIC: a domain whose best ungapped segment
+//   scores below T is lost, however well its gapped alignment scores.
 #pragma once
 #include <stdint.h>
 
@@ -109,6 +123,13 @@ SP_DM_HD inline int64_t sp_dm_match(int64_t m, int64_t i, int64_t d, int tmm, in
 }
 SP_DM_HD inline int64_t sp_dm_insert(int64_t m, int64_t i, int tmi, int tii) { return sp_dm_max(sp_dm_add(m, tmi), sp_dm_add(i, tii)); }
 SP_DM_HD inline int64_t sp_dm_delete(int64_t m, int64_t d, int tmd, int tdd) { return sp_dm_max(sp_dm_add(m, tmd), sp_dm_add(d, tdd)); }
+
+// the cell of the ungapped prefilter: prev = S[i-1][k-1] or SP_DM_SSV_NONE, tmm = tMM[k-1] (anything in range where prev is NONE)
+#define SP_DM_SSV_NONE (-(1 << 30))
+SP_DM_HD inline int32_t sp_dm_ssv_cell(int32_t prev, int tmm, int entry, int e) {
+    const int32_t through = prev + tmm;
+    return e + (through > entry ? through : entry);
+}
 
 // a hit: the word of the best M cell and where it ends; k = 0: no hit
 struct sp_dm_hit {
@@ -186,6 +207,22 @@ static inline sp_dm_hit sp_dm_host_frame(const uint8_t *res, int32_t nres, int M
         t = pM, pM = cM, cM = t;
         t = pI, pI = cI, cI = t;
         t = pD, pD = cD, cD = t;
+    }
+    return best;
+}
+// the ungapped prefilter of one frame against one profile; row: M + 1 int32 of scratch.  Row i overwrites row i - 1 in
+// place, from node M down, so that row[k - 1] still holds S[i-1][k-1] when node k reads it
+static inline int32_t sp_dm_host_ssv_frame(const uint8_t *res, int32_t nres, int M, const int32_t *emis, const int32_t *trans, int32_t entry,
+                                           int32_t *row) {
+    for (int k = 0; k <= M; k++) row[k] = SP_DM_SSV_NONE;
+    int32_t best = INT32_MIN;
+    for (int32_t i = 0; i < nres; i++) {
+        const int x = res[i];
+        for (int k = M; k >= 1; k--) {
+            const int32_t s = sp_dm_ssv_cell(row[k - 1], k >= 2 ? trans[7 * (k - 2) + SP_DM_MM] : 0, entry, emis[(int64_t)(k - 1) * SP_DM_COLS + x]);
+            row[k] = s;
+            if (s > best) best = s;
+        }
     }
     return best;
 }

@@ -30,6 +30,11 @@ STOP_COST = 2048               # SP_DM_STOPCOST: a stop codon costs 8 bits in ev
 COLS, COL_X, COL_STOP = 22, 20, 21
 MAX_M, MAX_LEN, MAX_P = 2048, 65536, 4096      # SP_DM_MAXM, SP_DM_MAXLEN, SP_DM_MAXP
 MIN_COV, MIN_SCORE = 20.0, 0.5                 # TEsorter's mincov and minscore (hmm2best)
+# -ltr_dom_prefilter without a value: the threshold of the ungapped prefilter in bits.  PROVISIONAL, set by a rule
+# (profiles/domains_notes.md): the smallest whole number of bits, of the 8..30 swept, at which at most 2 % of the (frame,
+# profile) pairs of random DNA pass (1.02 % at 8), on assumed profiles and synthetic DNA -- no REXdb, no calibration, no
+# comparison with hmmscan
+PREFILTER_BITS = 8
 # codons per amino acid of the standard code: the background is codons / 61.  PROVISIONAL: the composition of translated
 # random DNA, not HMMER's Swiss-Prot composition
 CODONS = dict(zip(AA, (4, 2, 2, 2, 2, 4, 2, 3, 2, 6, 1, 2, 4, 2, 6, 6, 4, 4, 1, 2)))

@@ -27,7 +27,8 @@ seeds, gapless extension; ltr.detect: the loop over the chromosomes and the chai
 -ltr_tree the subgenome-specific elements get ONE tree of this build's own: MinHash sketches and neighbour joining on the
 device (ltrtree.py, csrc/sp_ltrtree.hip), `.ltr.tree.nwk` / `.map` and a figure.  With -ltr_hmm the records are classified
 from the protein domains of their inner sequences first (domains.py, csrc/sp_domains.hip: this build's own Viterbi search of the
-user's profile HMMs, TEsorter's rules behind it): `.ltr.dom.gff3`, `.ltr.cls.tsv`, records that are no LTR-RTs dropped.  With
+user's profile HMMs, TEsorter's rules behind it): `.ltr.dom.gff3`, `.ltr.cls.tsv`, records that are no LTR-RTs dropped;
+-ltr_dom_prefilter searches only the (frame, profile) pairs whose best ungapped segment reaches a threshold (a heuristic).  With
 -ltr_domtree (and -ltr_hmm) the subgenome-specific elements that have all of -ltr_domains get one tree per Copia / Gypsy from
 their domains (domtree.py, csrc/sp_domalign.hip: this build's own profile alignment, occupancy trimming, Kimura distances and
 neighbour joining): `.ltr.cls.pep` and `.ltr.LTR_<Superfamily>.aln` / `.map` / `.aln.trimmed` / `.aln.rooted.tre` and a figure.
@@ -35,6 +36,7 @@ ltr_finder / ltrharvest themselves, TEsorter, mafft / trimal / iqtree and the ci
 """
 import argparse
 import io
+import math
 import os
 import pickle
 import shutil
@@ -180,6 +182,12 @@ CLI = [
         (("-ltr_dom_score",), dict(type=float, metavar="FLOAT", default=domains_mod.MIN_SCORE,
                                    help="minimum score of a domain in bits per node (TEsorter's 0.5); provisional: these bits are "
                                         "not HMMER's")),
+        (("-ltr_dom_prefilter",), dict(type=float, nargs="?", metavar="BITS", const=domains_mod.PREFILTER_BITS, default=None,
+                                       help="search only the (frame, profile) pairs whose best UNGAPPED segment scores at least "
+                                            "BITS bits (needs -ltr_hmm; without a value: {}); absent: every pair is searched.  A "
+                                            "heuristic that makes the search of many elements affordable: a domain whose best "
+                                            "ungapped segment scores below BITS is lost.  This build's rule, not HMMER's P-value "
+                                            "filter; the default is provisional".format(domains_mod.PREFILTER_BITS))),
         (("-ltr_tree",), dict(help="build ONE tree over the subgenome-specific LTR-RTs on the GPU and write `.ltr.tree.nwk`, "
                                    "`.ltr.tree.map` and `.ltr.tree.<figfmt>`: MinHash sketches of the elements' k-mers, Mash "
                                    "distances, neighbour joining, midpoint rooting.  Not a protein-domain tree and not one tree per "
@@ -250,6 +258,8 @@ def makeArgparse(argv=None):
         parser.error("-ltr_denovo detects the LTR-RTs, -ltr_scn reads them from a file: give one of the two")
     if args.ltr_domtree and not args.ltr_hmm:
         parser.error("-ltr_domtree builds its trees from the domains of the classification: give -ltr_hmm FILE as well")
+    if args.ltr_dom_prefilter is not None and not args.ltr_hmm:
+        parser.error("-ltr_dom_prefilter filters the domain search of the classification: give -ltr_hmm FILE as well")
     if args.prefix is not None:          # the prefix goes in front of directory names AND file names (__main__.py:242-245)
         args.prefix = args.prefix.replace("/", "_")
         args.outdir, args.tmpdir = args.prefix + args.outdir, args.prefix + args.tmpdir
@@ -776,6 +786,8 @@ class Pipeline:
             raise RuntimeError("-ltr_domtree needs a context with dom_align, dom_peptide, aln_pairs and nj_tree (libsubphaser_hip.so); "
                                "there is no CPU engine for the domain trees")
         self._want_domtree = bool(want_domtree)
+        if self.ltr_dom_prefilter is not None and not self.ltr_hmm:
+            raise ValueError("-ltr_dom_prefilter filters the domain search of the classification: give -ltr_hmm FILE as well")
         self._ltr_profiles, self._ltr_clades = None, {}
         if self.ltr_hmm:
             if not hasattr(ctx, "dom_search"):      # before anything is written
@@ -843,8 +855,11 @@ class Pipeline:
         if long_:
             logger.info("{} LTR-RTs with an inner sequence above {} bases are left unclassified".format(len(long_), domains_mod.MAX_LEN))
         pick = [q for q, (a, b) in enumerate(ival) if b - a <= domains_mod.MAX_LEN]
+        pre, passed = {}, {}
+        if self.ltr_dom_prefilter is not None:      # the ungapped prefilter: threshold in the search's units, 1/256 bit
+            pre = dict(prefilter=int(math.ceil(float(self.ltr_dom_prefilter) * domains_mod.SCALE)), stats=passed)
         hits = np.asarray(ctx.dom_search(np.array([index[known[q].seq_id] for q in pick], np.int32), np.array([ival[q][0] for q in pick], np.int64),
-                                         np.array([ival[q][1] for q in pick], np.int64), *profiles.tables())) if pick else np.zeros((0, len(profiles), 6), np.int32)
+                                         np.array([ival[q][1] for q in pick], np.int64), *profiles.tables(), **pre)) if pick else np.zeros((0, len(profiles), 6), np.int32)
         doms = domains_mod.best_domains([known[q].id for q in pick], [ival[q][1] - ival[q][0] for q in pick], hits, profiles,
                                         float(self.ltr_dom_cov), float(self.ltr_dom_score))
         rows = domains_mod.classify(doms)
@@ -855,9 +870,14 @@ class Pipeline:
         with open(cls, "w") as fout:
             domains_mod.write_cls(fout, rows)
         mk_ckp(lay.ckp(cls))
+        note = ""
+        if pre:
+            items, kept_items = int(passed.get("items", 0)), int(passed.get("passed", 0))
+            note = "; ungapped prefilter at {} bits: {} of {} (frame, profile) pairs ({:.2f}%) searched".format(
+                self.ltr_dom_prefilter, kept_items, items, 1e2 * kept_items / items if items else 0.0)
         logger.info("{} inner sequences x {} profiles searched in {:.2f} s: {} domains (coverage >= {}, score >= {} bits per node) in {} "
-                    "elements -> `{}`, `{}`".format(len(pick), len(profiles), time.perf_counter() - t0, len(doms), self.ltr_dom_cov,
-                                                    self.ltr_dom_score, len(rows), os.path.basename(gff), os.path.basename(cls)))
+                    "elements -> `{}`, `{}`{}".format(len(pick), len(profiles), time.perf_counter() - t0, len(doms), self.ltr_dom_cov,
+                                                      self.ltr_dom_score, len(rows), os.path.basename(gff), os.path.basename(cls), note))
         if self._want_domtree:
             self._ltr_dominfo = dict(doms=doms, rows=rows, where={known[q].id: (index[known[q].seq_id],) + tuple(ival[q]) for q in pick})
             self._ltr_pep(lay, ctx)
